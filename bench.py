@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark: FasterRCNN_R50_FPN forward+loss img/s (BASELINE.json metric, config 2).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,7 +19,13 @@ path (anchor targets, proposals+NMS, RCNN targets, RoIAlign) and the losses.
 Images are independent units: ranks share nothing on the data path
 ("scaling": "weak"); the forward+loss metric has no collective.
 
-After the timed region (never inside it):
+A plain run sets up, warms up, times `--steps` steps and prints one JSON line: `value`
+(img/s), `ms_per_step` and the configuration.  `--dump-outputs DIR` also writes what the last
+timed step returned (the loss dict's entries and their sum) as DIR/<name>.npy, float32; the
+model, the images and the samplers are seeded, so the inputs are the same from run to run.
+
+With `--full`, after the timed region (never inside it; the timed RoIAlign launches then go
+through the entry that records their own in-step clocks):
   * kernel lines: `--trace-steps` more steps run under the ROCm kernel tracer
     (torch.profiler / kineto), giving every hot-path kernel's in-step device
     duration and its dispatched name.  The RoIAlign `roofline` is computed from
@@ -529,6 +535,21 @@ def host_info():
             'omp_num_threads': os.environ.get('OMP_NUM_THREADS')}
 
 
+def dump_outputs(path, last):
+    """--dump-outputs: what the last timed step returned to its caller, one float32 DIR/<name>.npy
+    per array: every entry of forward_train's loss dict and their sum (`loss`, the step's own
+    float32 sum), or the train step's loss.  A few scalars: far below 64 MB.  Model, images and
+    boxes are seeded and the device sampler's seed is fixed, so two builds run with the same
+    arguments are compared output for output."""
+    if 'losses' in last:
+        arrays = dict(last['losses'], loss=sum(last['losses'].values()))
+    else:
+        arrays = {'loss': last['loss']}
+    os.makedirs(path, exist_ok=True)
+    for k, t in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), t.detach().float().cpu().numpy())
+
+
 def max_over_ranks(elapsed, dev, world):
     """Job time = the slowest rank's (weak scaling: every rank has its own shard)."""
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -628,16 +649,34 @@ def main():
                          'and wrap the detector in DDP anyway, so the bucketed all-reduce runs (RCCL readiness)')
     ap.add_argument('--conv-search', default='auto', choices=['auto', 'on', 'off'],
                     help='benchmark MIOpen convolution algorithms in the warmup (torch.backends.cudnn.benchmark; '
-                         '+5.8%% img/s on cfg2 fwd, ~1 min of search).  auto = on for fwd, off for train (the '
+                         '+5.8%% img/s on cfg2 fwd, ~1 min of search without --conv-search-iterations).  auto = on '
+                         'for fwd, off for train (the '
                          'backward-convolution search takes several minutes)')
     ap.add_argument('--no-conv-search', dest='conv_search', action='store_const', const='off')
+    ap.add_argument('--conv-search-iterations', type=int, default=None,
+                    help='most kernel configurations MIOpen tries per solver while it tunes a convolution in the '
+                         'search (MIOPEN_DEBUG_TUNING_ITERATIONS_MAX, unless the caller set it); 0 = no limit.  '
+                         'Default 32 for fwd: a first run with empty MIOpen databases then starts in ~23 s, not '
+                         'the minute of the unlimited search, at the same img/s within the run-to-run spread '
+                         '(DESIGN 7); no limit for train')
     ap.add_argument('--dump-rois', help='after the timed region, save the last RoIAlign launch\'s RoIs / levels / '
                          'level shapes / scales to this .npz (tests/golden/cfg2_rois_train.npz: the RoIs of a '
                          'training step, for tools/bench_roi_sets.py and the bit-exact RoIAlign test)')
     ap.add_argument('--graphs', default='auto', choices=['auto', 'on', 'off'],
                     help='replay backbone + neck + RPN head convs as one captured hipGraph (frcnn_amd.graphs) '
                          'after the warmup.  auto = on for fwd with a two-stage detector, off for train')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also measure the kernel lines, the RoIAlign roofline and replays '
+                         'and the CPU baselines (the module docstring; --trace-steps, --no-cpu-baseline, '
+                         '--cpu-baseline-seconds and --dump-rois act here).  Without it the run sets up, warms up, '
+                         'times the steps and prints the headline line only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed region, write what the last timed step returned to its caller (every '
+                         'entry of forward_train\'s loss dict and their sum; the loss in train mode) as '
+                         'DIR/<name>.npy, float32 (rank 0)')
     args = ap.parse_args()
+    if args.dump_rois and not args.full:
+        raise SystemExit('bench: --dump-rois records the launches of the steps after the timed region: needs --full')
     if args.mode == 'train' and 'MIOPEN_USER_DB_PATH' not in os.environ:
         # MIOpen's per-user database as a fresh box has it: after a forward-mode bench in the same
         # account, the train step's timed steps ran MIOpen's naive convolutions
@@ -680,6 +719,10 @@ def main():
     if args.conv_search == 'auto':
         args.conv_search = 'on' if args.mode == 'fwd' else 'off'
     args.conv_search = args.conv_search == 'on'
+    if args.conv_search_iterations is None:
+        args.conv_search_iterations = 32 if args.mode == 'fwd' else 0
+    if args.conv_search and args.conv_search_iterations > 0:  # read by MIOpen when it first tunes
+        os.environ.setdefault('MIOPEN_DEBUG_TUNING_ITERATIONS_MAX', str(args.conv_search_iterations))
     torch.backends.cudnn.benchmark = args.conv_search
     model, cfg = make_model(dev, seed=0, config=os.path.join(CONFIG_DIR, args.config + '.py'))
     batch = make_batch(dev, args.batch, seed=0, rank=rank)
@@ -692,11 +735,13 @@ def main():
                                force_ddp=force_ddp)
 
         def step():
-            return train_step(*batch)
+            last_outputs['loss'] = loss = train_step(*batch)
+            return loss
     else:
         def step():
-            losses = model.forward_train(*batch)
+            last_outputs['losses'] = losses = model.forward_train(*batch)
             return sum(losses.values())
+    last_outputs = {}  # what the newest step returned to its caller (references only; --dump-outputs)
 
     # Warmup (MIOpen's algorithm search runs here): a heartbeat on stderr keeps long
     # searches visibly alive (train mode searches the backward convolutions too).
@@ -739,15 +784,18 @@ def main():
     # kernel's own dispatch (frh_roi_align_fwd_strided_timed): its in-step duration, read after
     # the timed region; the events are created (recorded once) before it
     # plus a span slot each: the kernel's own first-wave-start / last-wave-end (100 MHz clock)
-    pool = []
-    spans = span_slots(4 * args.steps, dev)
-    for i in range(4 * args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        e1.record()
-        pool.append((e0, e1, spans[i]))
-    ops.ROI_ALIGN_PROFILE['event_pool'] = pool
-    ops.ROI_ALIGN_PROFILE['timed'] = timed_roi = []
+    # (--full only: a plain run's steps launch the product entry, frh_roi_align_fwd_strided)
+    timed_roi = []
+    if args.full:
+        pool = []
+        spans = span_slots(4 * args.steps, dev)
+        for i in range(4 * args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            e1.record()
+            pool.append((e0, e1, spans[i]))
+        ops.ROI_ALIGN_PROFILE['event_pool'] = pool
+        ops.ROI_ALIGN_PROFILE['timed'] = timed_roi
     barrier()
     roi_launches_before = ops.ROI_ALIGN_PROFILE['launches']  # warmup + graph-capture steps (step_breakdown)
     t0 = time.perf_counter()
@@ -762,10 +810,44 @@ def main():
     assert torch.isfinite(loss).all()
     ops.check_device_status(dev)  # the one-launch kernels' in-launch waits all completed (FRH_DEVERR_*)
     t_max = max_over_ranks(elapsed, dev, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs)
 
-    # ---- after the timed region: kernel lines (rank 0 only; other ranks idle)
     out = None
     if rank == 0:
+        imgs_total = world * args.batch * args.steps
+        out = {
+            'metric': 'img/s ' + CONFIG_NAMES[args.config] + ' 1000x600 ' + ('fwd+loss' if args.mode == 'fwd' else
+                                                               'train step (fwd+loss+bwd+allreduce+SGD)'),
+            'value': imgs_total / t_max,
+            'unit': 'img/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': 1e3 * t_max / args.steps,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32',
+            'data': 'synthetic images N(0,1) [B,3,608,1024], VOC07 trainval gt boxes, random-init weights',
+            'config': {'workload': 'configs/{}.py{} forward_train'.format(
+                           args.config, ' (BASELINE config 2)' if args.config == 'faster_rcnn_r50_fpn' else ''),
+                       'conv_algorithms': 'MIOpen benchmarked (warmup{})'.format(
+                           ', at most {} tuning iterations per solver'.format(
+                               os.environ['MIOPEN_DEBUG_TUNING_ITERATIONS_MAX'])
+                           if 'MIOPEN_DEBUG_TUNING_ITERATIONS_MAX' in os.environ else '')
+                       if args.conv_search else 'MIOpen heuristic',
+                       'trunk': 'hipGraph replay (backbone + neck + RPN head convs)' if graphed else 'eager',
+                       'global_batch': world * args.batch, 'imgs_per_gpu': args.batch,
+                       'image': '600x1000 padded 608x1024', 'parallelism': 'dp{}'.format(world),
+                       'backend': args.backend if world > 1 or force_ddp else None,
+                       'ddp': world > 1 or force_ddp if args.mode == 'train' else None,
+                       'sampler': args.sampler, 'mode': args.mode,
+                       'status_every': args.status_every if args.mode == 'train' else None},
+        }
+
+    # ---- --full, after the timed region: kernel lines (rank 0 only; other ranks idle)
+    if rank == 0 and args.full:
         ops.ROI_ALIGN_PROFILE['records'].clear()
         ops.NMS_PROFILE['records'].clear()
         ops.ROI_ALIGN_PROFILE['on'] = ops.NMS_PROFILE['on'] = True
@@ -821,32 +903,6 @@ def main():
                 traffic_note = 'stale: {} profiles {} but this run dispatched {}'.format(
                     os.path.relpath(pmc, REPO), names or pj.get('kernel'), roi_kernel)
 
-        imgs_total = world * args.batch * args.steps
-        out = {
-            'metric': 'img/s ' + CONFIG_NAMES[args.config] + ' 1000x600 ' + ('fwd+loss' if args.mode == 'fwd' else
-                                                               'train step (fwd+loss+bwd+allreduce+SGD)'),
-            'value': imgs_total / t_max,
-            'unit': 'img/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': 1e3 * t_max / args.steps,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f32',
-            'data': 'synthetic images N(0,1) [B,3,608,1024], VOC07 trainval gt boxes, random-init weights',
-            'config': {'workload': 'configs/{}.py{} forward_train'.format(
-                           args.config, ' (BASELINE config 2)' if args.config == 'faster_rcnn_r50_fpn' else ''),
-                       'conv_algorithms': 'MIOpen benchmarked (warmup)' if args.conv_search else 'MIOpen heuristic',
-                       'trunk': 'hipGraph replay (backbone + neck + RPN head convs)' if graphed else 'eager',
-                       'global_batch': world * args.batch, 'imgs_per_gpu': args.batch,
-                       'image': '600x1000 padded 608x1024', 'parallelism': 'dp{}'.format(world),
-                       'backend': args.backend if world > 1 or force_ddp else None,
-                       'ddp': world > 1 or force_ddp if args.mode == 'train' else None,
-                       'sampler': args.sampler, 'mode': args.mode,
-                       'status_every': args.status_every if args.mode == 'train' else None},
-        }
         if recs:
             out['roofline'] = {
                 'kernel': roi_kernel or 'frh_roi_align_fwd_strided (name unavailable: {})'.format(trace_err),
@@ -952,6 +1008,7 @@ def main():
                 out['cpu_baseline'] = cpu_baseline(0, args.cpu_baseline_seconds)
             except Exception as e:
                 out['cpu_baseline'] = {'value': None, 'error': repr(e)[:200]}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -6,7 +6,7 @@ product.
 Sets (tests/golden): bench = cfg2_rois.npz (the RoIs of a random-init cfg2 step), voc =
 cfg2_rois_voc.npz (gen_voc_rois.py: the RCNN sampler's mix around the bench images' VOC
 gts), train = cfg2_rois_train.npz (a `bench.py --mode train` step's RoIs, dumped by
-`bench.py --dump-rois`).  Features: N(0,1) channels-last P2-P5 of the set's shapes, C = 256
+`bench.py --full --dump-rois`).  Features: N(0,1) channels-last P2-P5 of the set's shapes, C = 256
 (the product trunk's FPN layout).  The round-4 library (tools/lib/r4/libfrcnn_amd_r4.so,
 built from the round-4 commit by tools/build_r4_lib.sh) is the A/B reference for the
 kernel that shipped then: 8-KB slab, per-lane global gathers for tap grids > 512 cells."""

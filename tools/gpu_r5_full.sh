@@ -7,7 +7,7 @@ tail -5 $O/tests/pytest.log
 grep -E "FAILED|ERROR" $O/tests/pytest.log | head -20
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench.json'))
 print('value', d['value'], 'ms', d['ms_per_step']); r=d['roofline']; print('roi', r['avg_launch_us'], r['frac'], 'in-step', r['in_step_span_us_median'], r['frac_in_step'])

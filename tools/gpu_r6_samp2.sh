@@ -10,7 +10,7 @@ python -c "
 import json;d=json.load(open('$O/select.json'));s=d['sampler'];print('sampler us/call', s['us_per_call_one_launch'], 'two-launch', s['us_per_call_two_launches'])
 [print(' ', k, v['rel_wg_start_us'], v['rel_launch_us_median'], v['rel_launch_us_max']) for k, v in s['timeline_one_launch'].items()]
 print('proposals us/call', d['rpn_proposals']['us_per_call_one_launch_select'])"
-timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print(round(d['value'],1), d['ms_per_step'], d['kernels']['detection_path_kernels_us_per_step'])"
 # last: the subset whose order exposed the unranked repeated-selection rows (round 6)

@@ -2,6 +2,6 @@
 set -o pipefail
 O=${1:-gpurun_out/r4_full}; mkdir -p $O; export TMPDIR=/tmp
 bash tools/gpu_tests.sh $O/tests && \
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err && \
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err && \
 bash tools/profile_round.sh $O/prof && \
 timeout -k 10 120 rocprofv3 --list-avail > $O/counters.txt 2>&1

@@ -4,7 +4,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-me
 rc=$?
 echo "pytest rc=$rc" >> $O/pytest.log
 if [ $rc -eq 0 ] || [ $rc -eq 1 ]; then
-  timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err
   echo "bench rc=$?" >> $O/bench.err
 fi
 exit $rc

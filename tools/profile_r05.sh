@@ -11,16 +11,16 @@ K=roi_align_fwd_band_kernel
 mkdir -p $OUT
 export TMPDIR=/tmp
 run() { timeout -k 10 "$@"; }
-run 300 python bench.py --no-cpu-baseline > $OUT/bench_plain.json 2> $OUT/bench_plain.err || exit 1
-run 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || exit 1
+run 300 python bench.py --full --no-cpu-baseline > $OUT/bench_plain.json 2> $OUT/bench_plain.err || exit 1
+run 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || exit 1
 # the timed steps start after the warmup AND the graph-capture steps: the bench line says where
 W=$(python -c "import json; print(json.loads(open('$OUT/bench_under_rocprof.json').read().strip().splitlines()[-1])['roofline']['launches_before_timed_region'])")
 python tools/step_breakdown.py $OUT/stats --warmup $W --steps 10 > $OUT/step_breakdown.json || exit 1
 rm -f $OUT/stats/run_kernel_trace.csv
 for m in fwd train; do
   A="--steps 3 --warmup 2 --no-cpu-baseline --trace-steps 0 --mode $m"
-  run 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch_$m -o run --output-format csv -- python bench.py $A > $OUT/pmc_fetch_$m.log 2>&1 || exit 1
-  run 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write_$m -o run --output-format csv -- python bench.py $A > $OUT/pmc_write_$m.log 2>&1 || exit 1
+  run 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch_$m -o run --output-format csv -- python bench.py --full $A > $OUT/pmc_fetch_$m.log 2>&1 || exit 1
+  run 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write_$m -o run --output-format csv -- python bench.py --full $A > $OUT/pmc_write_$m.log 2>&1 || exit 1
 done
 run 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_calib_small -o run --output-format csv -- python tools/bench_roi_align.py --calib --calib-small --variants 50 > $OUT/pmc_calib_small.log 2>&1 || exit 1
 run 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_calib_band -o run --output-format csv -- python tools/bench_roi_align.py --calib --variants 50 > $OUT/pmc_calib_band.log 2>&1 || exit 1

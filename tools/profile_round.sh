@@ -10,7 +10,7 @@ K=${2:-roi_align_fwd_quad_kernel}
 CV=${3:-10}
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/stats.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/stats.log 2>&1
 python tools/step_breakdown.py $OUT/stats --warmup 3 --steps 10 > $OUT/step_breakdown.json
 rm -f $OUT/stats/run_kernel_trace.csv  # large; the summary and the breakdown are kept
 mkdir -p $OUT/disp $OUT/disp_tracer
