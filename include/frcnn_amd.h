@@ -149,6 +149,43 @@ int32_t frh_sample_random(int32_t num_segs, const int64_t* labels_in, int64_t la
                           int32_t* sel_counts, int32_t* status, void* workspace, size_t ws_bytes,
                           void* stream);
 
+/* ---- a5b: IoUBalancedNegSampler -----------------------------------------------
+ * Replaces lib/region.py:128-172.  Per image: kp = min(#positives, pos_num) positives are
+ * kept; num_neg = max_num - kp; the negatives (label == 0) are binned by their IoU
+ * (row i's IoU is ious[s * iou_seg_stride + i - iou_offsets[s]]: frh_maxiou_assign's max_iou,
+ * with iou_offsets (device int32 [S], NULL = 0) the number of rows frh_prepend_gt_labels put
+ * in front; read for label == 0 rows only, so the prepended ground truth needs no value) into num_bins (1..8) bins
+ * bin_lo[j] <= iou < bin_hi[j] (host arrays, ascending, computed by the caller with the
+ * reference's i*bin_size / s+bin_size and rounded to f32; bins that overlap are refused
+ * with FRH_EINVAL where the reference would count a box twice).  Bins are visited from the
+ * highest to the lowest; each but the lowest takes min(count, int(num_neg / num_bins)), the
+ * lowest min(count, num_neg - taken so far); negatives in no bin (iou >= max_iou) are never
+ * chosen and the total may stay below max_num (region.py:158-165).
+ *  device mode: frh_sample_iou_balanced; each class (the positives, each bin) keeps its
+ *   quota uniformly without replacement by the extreme hash(seed, class, box) keys, as
+ *   frh_sample_random.  Outputs as frh_sample_random's (labels_out and / or sel
+ *   [S][2][max_num] + sel_counts [S][2], every bin's choices in the negatives' list), so
+ *   frh_bbox_target consumes them unchanged.  One workgroup per (class, image), no
+ *   cross-workgroup wait: no status word and no workspace.  Images above 16 384 rows
+ *   return FRH_EUNSUPPORTED.
+ *  reference-RNG parity: frh_sample_iou_candidates lists, per image s and class w (0 the
+ *   positives, 1 + j the j-th VISITED bin, i.e. the highest bin first), the class's rows in
+ *   ascending order at lists[(s * (1 + num_bins) + w) * list_ld ..] and their number in
+ *   counts[s * (1 + num_bins) + w]; the host draws the reference's np.random.choice per
+ *   over-full class and frh_sample_apply keeps the chosen positions (pos_list = the class-0
+ *   list, neg_list = the class-1 list with positions j * list_ld + p for bin j, segment
+ *   stride (1 + num_bins) * list_ld).  Same row capacity. */
+int32_t frh_sample_iou_balanced(int32_t num_segs, const int64_t* labels_in, int64_t label_seg_stride,
+                                const float* ious, int64_t iou_seg_stride, const int32_t* iou_offsets,
+                                const int32_t* num_boxes, int64_t max_boxes, int32_t max_num, int32_t pos_num, int32_t num_bins,
+                                const float* bin_lo, const float* bin_hi, uint64_t seed,
+                                int64_t* labels_out, int32_t* sel, int32_t* sel_counts, void* stream);
+int32_t frh_sample_iou_candidates(int32_t num_segs, const int64_t* labels, int64_t label_seg_stride,
+                                  const float* ious, int64_t iou_seg_stride, const int32_t* iou_offsets,
+                                  const int32_t* num_boxes, int64_t max_boxes, int32_t num_bins, const float* bin_lo,
+                                  const float* bin_hi, int32_t* lists, int64_t list_ld, int32_t* counts,
+                                  void* stream);
+
 /* ---- a6: anchor_target (lib/anchor.py:11-76) after assign+sample -------------
  * Chosen = boxes with sampled label >= 0, ascending.  Segment outputs are
  * concatenated in segment order (the reference's per-image results followed
@@ -499,6 +536,35 @@ int32_t frh_fpn_merge_nhwc(const float* lat, const int64_t* lat_strides, const f
                            int32_t up_h, int32_t up_w, float* out, int32_t batch, int32_t channels, int32_t height,
                            int32_t width, void* stream);
 
+/* BFP neck, refine_type=None (lib/necks.py:93-141, BFP.forward): with r = refine_level,
+ * refine = (sum over i != r, in level order, of [i < r: adaptive_max_pool2d(feats[i],
+ * size_r); i > r: interpolate(feats[i], size_r, 'nearest')]) / (num_levels - 1) and
+ * out[i] = feats[i] + [i < r: interpolate(refine, size_i, 'nearest'); i > r:
+ * adaptive_max_pool2d(refine, size_i); i == r: refine], with torch's index rules (window
+ * [floor(o*in/out), ceil((o+1)*in/out)), nearest min(floor(d * (float)in / out), in - 1)) and
+ * its CPU maximum (row-major scan, `>` or NaN replaces).  Two launches; bit-identical to the
+ * reference on the CPU.  2 <= num_levels <= FRH_MAX_LEVELS, any refine_level, any level
+ * sizes up to 32767 (level_hw[2i], level_hw[2i+1] = H_i, W_i; host array), channels >= 1
+ * (16-byte lanes when channels % 4 == 0 and strides / pointers allow, scalar otherwise).
+ * feats[i] (host array of device pointers): f32 with element strides level_strides[4i..] =
+ * (b, c, y, x), any layout; refine [batch, H_r, W_r, channels] and outs[i] NHWC contiguous.
+ * argmax (nullable; frh_bfp_argmax_elems() int32 elements): the winning cell y*W + x of every
+ * window, for frh_bfp_bwd.
+ * Backward: grad_feats[i] (NHWC contiguous; entry refine_level is not written and may be
+ * NULL: that gradient is grad_outs[refine_level] itself) from grad_outs[i] (strides
+ * grad_strides), routing the max-pool gradients to the stored argmax cells (a cell that is
+ * the argmax of several overlapping windows gets their sum); grad_refine [batch, H_r, W_r,
+ * channels] is scratch.  Two launches, gathers in a fixed order: deterministic, no atomics. */
+size_t frh_bfp_argmax_elems(int32_t num_levels, int32_t refine_level, int32_t batch, int32_t channels,
+                            const int32_t* level_hw);
+int32_t frh_bfp_fwd(int32_t num_levels, int32_t refine_level, int32_t batch, int32_t channels,
+                    const void* const* feats, const int32_t* level_hw, const int64_t* level_strides,
+                    float* refine, void* const* outs, int32_t* argmax, int64_t argmax_elems, void* stream);
+int32_t frh_bfp_bwd(int32_t num_levels, int32_t refine_level, int32_t batch, int32_t channels,
+                    const void* const* grad_outs, const int32_t* level_hw, const int64_t* grad_strides,
+                    const int32_t* argmax, int64_t argmax_elems, float* grad_refine,
+                    void* const* grad_feats, void* stream);
+
 /* Conv epilogue on a channels-last map viewed as [rows, channels] (rows = batch * H * W):
  * y = relu ? max(y + bias[c], 0) : y + bias[c], in place -- the RPN head's
  * relu(conv(x)) (lib/heads/rpn_head.py, RPNHead.forward) after a bias-free NHWC conv, one
@@ -545,6 +611,21 @@ int32_t frh_smooth_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs
                           int64_t n, int64_t m, int64_t n_sel, float beta,
                           const float* grad_out, float* grad_x, int64_t gs_i, int64_t gs_j,
                           int64_t gs_l, void* stream);
+/* balanced_l1_loss (losses.py:158-180, BalancedL1Loss): frh_smooth_l1_fwd / _bwd with the
+ * element, for d = |x - y| and b = e^(gamma / alpha) - 1,
+ *   d < beta ? alpha / b * (b*d + 1) * log(b*d / beta + 1) - alpha*d : gamma*d + gamma / b - alpha*beta
+ * (f32, in the reference's operation order) and its derivative times sign(x - y) backward.
+ * Same strided access, label mask / class select, status word and workspace. */
+int32_t frh_balanced_l1_fwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l,
+                            const float* y, int64_t ys_i, int64_t ys_j, const int64_t* label,
+                            int64_t n, int64_t m, int64_t n_sel, float beta, float alpha, float gamma,
+                            const int32_t* status, float* out, void* workspace, size_t ws_bytes,
+                            void* stream);
+int32_t frh_balanced_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l,
+                            const float* y, int64_t ys_i, int64_t ys_j, const int64_t* label,
+                            int64_t n, int64_t m, int64_t n_sel, float beta, float alpha, float gamma,
+                            const float* grad_out, float* grad_x, int64_t gs_i, int64_t gs_j,
+                            int64_t gs_l, void* stream);
 /* One head's two losses in ONE launch, scaled as the heads scale them: out[0] =
  * (cls_sum * cls_weight) / cls_div, out[1] = (reg_sum * reg_weight) / reg_div (f32), cls_sum
  * as frh_cls_loss_fwd, reg_sum as frh_smooth_l1_fwd (both sums bit-identical to theirs).

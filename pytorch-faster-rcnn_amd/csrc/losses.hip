@@ -1,9 +1,11 @@
 // Fused detection losses: classification (sigmoid focal,
-// sigmoid BCE, softmax cross-entropy) and masked / class-selected smooth-L1,
-// forward sums and backward gradients, straight from the head outputs.
+// sigmoid BCE, softmax cross-entropy) and masked / class-selected smooth-L1
+// and balanced L1, forward sums and backward gradients, straight from the
+// head outputs.
 //
 // Reference: lib/losses.py:33-61 (sigmoid_focal_loss), :77-83
-// (smooth_l1_loss_v2), :126-156 (CrossEntropyLoss), and their callers
+// (smooth_l1_loss_v2), :126-156 (CrossEntropyLoss), :158-180
+// (balanced_l1_loss / BalancedL1Loss), and their callers
 // AnchorHead.calc_loss (lib/heads/anchor_head.py:113-139) and
 // BBoxHead.calc_loss (lib/heads/bbox_head.py:56-87).  The reference builds a
 // one-hot target, a sigmoid, pt, a focal weight, BCE-with-logits and a sum as
@@ -256,7 +258,7 @@ struct L1Args {
   float beta;
 };
 
-// smooth_l1_loss_v2 element (losses.py:77-83): d < beta ? d^2 / (2 beta) : d - beta / 2
+// row i of a regression loss: masked out, or the offset of its (class-selected) first element
 __device__ __forceinline__ bool l1_row(const L1Args& a, int64_t i, int64_t* off) {
   int64_t l = a.label ? a.label[i] : 0;
   if (a.label && l <= 0) return false;
@@ -264,7 +266,33 @@ __device__ __forceinline__ bool l1_row(const L1Args& a, int64_t i, int64_t* off)
   return true;
 }
 
-__global__ void __launch_bounds__(kLossThreads) smooth_l1_fwd_kernel(L1Args a, FanIn f) {
+// The regression element as a function of d = |x - y| and its slope; the kernels below are
+// shared by every such loss (strided access, label mask / class select, status-word NaN,
+// in-launch finalisation).
+struct SmoothL1Elem {  // smooth_l1_loss_v2 (losses.py:77-83)
+  float beta;
+  __device__ __forceinline__ float value(float d) const { return d < beta ? (d * d) / (2.0f * beta) : d - 0.5f * beta; }
+  __device__ __forceinline__ float slope(float d) const { return d < beta ? (2.0f * d) / (2.0f * beta) : 1.0f; }
+};
+
+// balanced_l1_loss (losses.py:158-168), in the reference's operation order with its Python
+// scalars rounded to f32 as torch does: d < beta ? alpha / b * (b * d + 1) * log(b * d / beta + 1)
+// - alpha * d : gamma * d + gamma / b - alpha * beta, b = e^(gamma / alpha) - 1.
+struct BalancedL1Elem {
+  float beta, alpha, gamma, b, a_over_b, g_over_b, ab;
+  __device__ __forceinline__ float value(float d) const {
+    const float bd = b * d;
+    return d < beta ? (a_over_b * (bd + 1.0f)) * logf(bd / beta + 1.0f) - alpha * d : (gamma * d + g_over_b) - ab;
+  }
+  // d/dd of the above: alpha * log(b d / beta + 1) + alpha (b d + 1) / (b d + beta) - alpha, or gamma
+  __device__ __forceinline__ float slope(float d) const {
+    const float bd = b * d;
+    return d < beta ? (alpha * logf(bd / beta + 1.0f) + (alpha * (bd + 1.0f)) / (bd + beta)) - alpha : gamma;
+  }
+};
+
+template <class Elem>
+__global__ void __launch_bounds__(kLossThreads) l1_fwd_kernel(L1Args a, Elem el, FanIn f) {
   __shared__ float scratch[kLossThreads / kWave];
   float acc = 0.0f;
   const int64_t total = a.n * a.m;
@@ -277,14 +305,15 @@ __global__ void __launch_bounds__(kLossThreads) smooth_l1_fwd_kernel(L1Args a, F
       continue;
     }
     float d = fabsf(a.x[off + j * a.xs_j] - a.y[i * a.ys_i + j * a.ys_j]);
-    acc += d < a.beta ? (d * d) / (2.0f * a.beta) : d - 0.5f * a.beta;
+    acc += el.value(d);
   }
   fan_in_finalize(block_sum_f(acc, scratch), f);
 }
 
 // gx must be zero-filled by the caller: only the selected, unmasked elements are written.
-__global__ void __launch_bounds__(kLossThreads) smooth_l1_bwd_kernel(L1Args a, const float* gout, float* gx,
-                                                                     int64_t gs_i, int64_t gs_j, int64_t gs_l) {
+template <class Elem>
+__global__ void __launch_bounds__(kLossThreads) l1_bwd_kernel(L1Args a, Elem el, const float* gout, float* gx,
+                                                              int64_t gs_i, int64_t gs_j, int64_t gs_l) {
   const float g = *gout;
   const int64_t total = a.n * a.m;
   for (int64_t e = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; e < total;
@@ -296,7 +325,7 @@ __global__ void __launch_bounds__(kLossThreads) smooth_l1_bwd_kernel(L1Args a, c
     float diff = a.x[off + j * a.xs_j] - a.y[i * a.ys_i + j * a.ys_j];
     float d = fabsf(diff);
     float sgn = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f);
-    float dd = d < a.beta ? (2.0f * d) / (2.0f * a.beta) : 1.0f;
+    float dd = el.slope(d);
     gx[i * gs_i + j * gs_j + l * gs_l] = g * dd * sgn;
   }
 }
@@ -304,7 +333,7 @@ __global__ void __launch_bounds__(kLossThreads) smooth_l1_bwd_kernel(L1Args a, c
 // Classification + regression loss of one head in ONE launch (AnchorHead / BBoxHead
 // calc_loss with a sampler: anchor_head.py:113-139, bbox_head.py:56-87).  Workgroup b
 // takes the cls elements of workgroup b of cls_loss_fwd_kernel's grid (b < nbc) and the
-// smooth-L1 elements of workgroup b of smooth_l1_fwd_kernel's grid (b < nbr); the last
+// smooth-L1 elements of workgroup b of l1_fwd_kernel<SmoothL1Elem>'s grid (b < nbr); the last
 // workgroup to arrive sums each loss's partials in the fixed order of fan_in_finalize,
 // so both sums equal the separate launches' bit for bit, and applies the heads' scaling
 // as torch does it: loss = (sum * loss_weight) / avg_factor in f32.
@@ -471,6 +500,31 @@ L1Args make_l1(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const f
   return a;
 }
 
+int32_t make_balanced(float beta, float alpha, float gamma, BalancedL1Elem* el) {
+  FRH_REQUIRE(alpha > 0.0f && gamma > 0.0f, "balanced l1: alpha and gamma must be > 0");
+  const double b = exp((double)gamma / (double)alpha) - 1.0;
+  *el = BalancedL1Elem{beta, alpha, gamma, (float)b, (float)((double)alpha / b), (float)((double)gamma / b),
+                       (float)((double)alpha * (double)beta)};
+  return FRH_OK;
+}
+
+template <class Elem>
+int32_t launch_l1_fwd(const L1Args& a, const Elem& el, const FanIn& f, void* stream, const char* what) {
+  hipLaunchKernelGGL(l1_fwd_kernel<Elem>, dim3(grid_for(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
+                     f);
+  return check_launch(what);
+}
+
+template <class Elem>
+int32_t launch_l1_bwd(const L1Args& a, const Elem& el, const float* grad_out, float* grad_x, int64_t gs_i,
+                      int64_t gs_j, int64_t gs_l, void* stream, const char* what) {
+  FRH_REQUIRE(grad_out && (a.n == 0 || grad_x), "l1 bwd: null gradient");
+  if (a.n == 0) return FRH_OK;
+  hipLaunchKernelGGL(l1_bwd_kernel<Elem>, dim3(grid_for(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
+                     grad_out, grad_x, gs_i, gs_j, gs_l);
+  return check_launch(what);
+}
+
 }  // namespace
 }  // namespace frh
 
@@ -534,10 +588,22 @@ int32_t frh_smooth_l1_fwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs
   if (st != FRH_OK) return st;
   FRH_REQUIRE(out, "smooth l1: null output");
   FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "smooth l1: workspace too small");
-  int nb = grid_for(n * m);
-  hipLaunchKernelGGL(smooth_l1_fwd_kernel, dim3(nb), dim3(kLossThreads), 0, as_stream(stream), a,
-                     fan_in(workspace, out, status));
-  return check_launch("frh_smooth_l1_fwd");
+  return launch_l1_fwd(a, SmoothL1Elem{beta}, fan_in(workspace, out, status), stream, "frh_smooth_l1_fwd");
+}
+
+int32_t frh_balanced_l1_fwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const float* y, int64_t ys_i,
+                            int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
+                            float alpha, float gamma, const int32_t* status, float* out, void* workspace,
+                            size_t ws_bytes, void* stream) {
+  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
+  int32_t st = check_l1(a);
+  if (st != FRH_OK) return st;
+  BalancedL1Elem el;
+  st = make_balanced(beta, alpha, gamma, &el);
+  if (st != FRH_OK) return st;
+  FRH_REQUIRE(out, "balanced l1: null output");
+  FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "balanced l1: workspace too small");
+  return launch_l1_fwd(a, el, fan_in(workspace, out, status), stream, "frh_balanced_l1_fwd");
 }
 
 int32_t frh_det_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int64_t sr, int64_t sc,
@@ -579,11 +645,20 @@ int32_t frh_smooth_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs
   L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
   int32_t st = check_l1(a);
   if (st != FRH_OK) return st;
-  FRH_REQUIRE(grad_out && (n == 0 || grad_x), "smooth l1 bwd: null gradient");
-  if (n == 0) return FRH_OK;
-  hipLaunchKernelGGL(smooth_l1_bwd_kernel, dim3(grid_for(n * m)), dim3(kLossThreads), 0, as_stream(stream), a,
-                     grad_out, grad_x, gs_i, gs_j, gs_l);
-  return check_launch("frh_smooth_l1_bwd");
+  return launch_l1_bwd(a, SmoothL1Elem{beta}, grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_smooth_l1_bwd");
+}
+
+int32_t frh_balanced_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const float* y, int64_t ys_i,
+                            int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
+                            float alpha, float gamma, const float* grad_out, float* grad_x, int64_t gs_i,
+                            int64_t gs_j, int64_t gs_l, void* stream) {
+  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
+  int32_t st = check_l1(a);
+  if (st != FRH_OK) return st;
+  BalancedL1Elem el;
+  st = make_balanced(beta, alpha, gamma, &el);
+  if (st != FRH_OK) return st;
+  return launch_l1_bwd(a, el, grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_balanced_l1_bwd");
 }
 
 }  // extern "C"

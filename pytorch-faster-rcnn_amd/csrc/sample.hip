@@ -877,6 +877,170 @@ __global__ void __launch_bounds__(kSsThreads) sampler_small_kernel(const int64_t
   if (sel && t == 0) sel_cnt[v] = k > 0 ? k : 0;
 }
 
+// IoUBalancedNegSampler (lib/region.py:128-172) in sampler_small_kernel's form: one
+// workgroup per (class, image), the classes being the positives (label > 0) and, per IoU
+// bin in the reference's visiting order (highest bin first), the negatives (label == 0)
+// with lo <= iou < hi.  Every workgroup counts every class (a bin's quota depends on what
+// the bins above it took: region.py:158), then selects its own class's k extreme keys
+// hash(seed, class, box) exactly as the random sampler does.  Negatives outside every bin
+// (iou >= max_iou, NaN) are never chosen.
+constexpr int kIbMaxBins = 8;
+constexpr int kIbClasses = kIbMaxBins + 1;
+constexpr int kIbNoBin = kIbClasses;  // a negative outside every bin
+constexpr int kIbIgnore = -1;
+
+struct IbEdges {  // bins in visiting order: [0] is the highest
+  float lo[kIbMaxBins], hi[kIbMaxBins];
+  int nb;
+};
+
+// class of a row: 0 positives, 1 + j = j-th visited bin, kIbNoBin, kIbIgnore
+__device__ __forceinline__ int ib_class(int64_t lab, const float* iou, int64_t i, const IbEdges& e) {
+  if (lab > 0) return 0;
+  if (lab < 0) return kIbIgnore;
+  const float u = iou[i];
+  int c = kIbNoBin;
+#pragma unroll
+  for (int j = kIbMaxBins - 1; j >= 0; --j)
+    if (j < e.nb && u >= e.lo[j] && u < e.hi[j]) c = 1 + j;
+  return c;
+}
+
+struct IbQuota {
+  int k, offset, neg_total;  // this class's quota, its first slot in its list, all bins' takes
+};
+
+// region.py:145-161 from the class counts tot[0 .. nb]
+__device__ __forceinline__ IbQuota ib_quota(const int (&tot)[kIbClasses], int nb, int max_num, int pos_num, int w) {
+  const int kp = tot[0] < pos_num ? tot[0] : pos_num;
+  const int num_neg = max_num - kp, per_bin = num_neg / nb;
+  IbQuota q{w == 0 ? kp : 0, 0, 0};
+  int chosen = 0;
+#pragma unroll
+  for (int j = 0; j < kIbMaxBins; ++j) {
+    if (j >= nb) break;
+    const int allowed = j < nb - 1 ? per_bin : num_neg - chosen;
+    const int tk = tot[1 + j] < allowed ? tot[1 + j] : allowed;
+    if (w == 1 + j) q.k = tk, q.offset = chosen;
+    chosen += tk;
+  }
+  q.neg_total = chosen;
+  return q;
+}
+
+// grid (1 + num_bins, images)
+__global__ void __launch_bounds__(kSsThreads) sampler_iou_kernel(const int64_t* lab_in, int64_t lstride,
+                                                                 const float* iou, int64_t istride,
+                                                                 const int32_t* ioff, const int32_t* num, int max_num,
+                                                                 int pos_num, uint64_t seed, IbEdges e,
+                                                                 int64_t* lab_out, int32_t* sel, int64_t sel_ld,
+                                                                 int32_t* sel_cnt) {
+  __shared__ uint32_t h[256];
+  __shared__ int scratch[kSsThreads / kWave];
+  __shared__ int sh[4];
+  __shared__ int slot;
+  __shared__ int part[kSsThreads / kWave];
+  const int w = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
+  const int v = s * (e.nb + 1) + w;
+  const int n = num[s], goff = ioff ? ioff[s] : 0;
+  int64_t lab[kSsPer];
+  uint32_t key[kSsPer];
+  uint32_t own = 0u;  // bit r: element r is written by this workgroup (labels_out)
+  int cnt[kIbClasses];
+#pragma unroll
+  for (int q = 0; q < kIbClasses; ++q) cnt[q] = 0;
+#pragma unroll
+  for (int r = 0; r < kSsPer; ++r) {
+    const int i = r * kSsThreads + t;
+    lab[r] = i < n ? lab_in[(int64_t)s * lstride + i] : -1;
+  }
+#pragma unroll
+  for (int r = 0; r < kSsPer; ++r) {
+    const int i = r * kSsThreads + t;
+    const int c = ib_class(lab[r], iou + (int64_t)s * istride, (int64_t)i - goff, e);
+#pragma unroll
+    for (int q = 0; q < kIbClasses; ++q) cnt[q] += c == q;
+    // the positives' workgroup also writes the rows no bin owns
+    own |= (c == w || (w == 0 && (c == kIbIgnore || c == kIbNoBin))) ? 1u << r : 0u;
+    key[r] = c == w ? ((~hash_u32(seed, (uint32_t)v, (uint32_t)i)) | 1u) : 0u;
+  }
+  int tot[kIbClasses];
+#pragma unroll
+  for (int q = 0; q < kIbClasses; ++q) tot[q] = q <= e.nb ? block_sum(cnt[q], scratch) : 0;
+  const IbQuota qu = ib_quota(tot, e.nb, max_num, pos_num, w);
+  int c = 0;
+#pragma unroll
+  for (int q = 0; q < kIbClasses; ++q) c = q == w ? tot[q] : c;
+  const int k = qu.k;
+  uint32_t take = 0u;  // bit r: element r taken
+  if (k > 0 && k >= c) {  // every candidate
+#pragma unroll
+    for (int r = 0; r < kSsPer; ++r) take |= key[r] != 0u ? 1u << r : 0u;
+  } else if (k > 0) {
+    const SsPlan pl = ss_plan(key, k, h, sh);
+    const int sh_p = 32 - pl.pb;
+    uint32_t tie = 0u;
+#pragma unroll
+    for (int r = 0; r < kSsPer; ++r) {
+      const uint32_t pre = key[r] >> sh_p;
+      if (key[r] != 0u && pre > pl.P) take |= 1u << r;
+      if (key[r] != 0u && pre == pl.P) tie |= 1u << r;
+    }
+    if (pl.all) {
+      take |= tie;
+    } else {  // the first pl.k tied keys by ascending box
+      int before = 0;
+      for (int r = 0; r < kSsPer; ++r) {
+        if (r * kSsThreads >= n) break;
+        int tt;
+        const bool f = (tie >> r) & 1u;
+        const int rk = block_rank(f, part, &tt);
+        if (f && before + rk < pl.k) take |= 1u << r;
+        before += tt;
+      }
+    }
+  }
+  if (t == 0) slot = 0;
+  __syncthreads();
+  int32_t* list = sel ? sel + (int64_t)(2 * s + (w ? 1 : 0)) * sel_ld + qu.offset : nullptr;
+#pragma unroll
+  for (int r = 0; r < kSsPer; ++r) {
+    if (r * kSsThreads >= n) break;
+    const int i = r * kSsThreads + t;
+    const bool tk = (take >> r) & 1u;
+    if (lab_out && i < n && ((own >> r) & 1u)) lab_out[(int64_t)s * lstride + i] = tk ? lab[r] : -1;
+    if (sel) {
+      const int sp = wave_append(tk, &slot);
+      if (tk) list[sp] = i;
+    }
+  }
+  if (sel && t == 0 && w <= 1) sel_cnt[2 * s + w] = w == 0 ? k : qu.neg_total;
+}
+
+// The numpy-parity mode's candidate lists: class w's rows of image s in ascending order at
+// lists[(s * (1 + nb) + w) * ld ..], their number in counts[s * (1 + nb) + w].
+__global__ void __launch_bounds__(kSsThreads) sampler_iou_lists_kernel(const int64_t* lab_in, int64_t lstride,
+                                                                       const float* iou, int64_t istride,
+                                                                       const int32_t* ioff, const int32_t* num,
+                                                                       IbEdges e, int32_t* lists, int64_t ld,
+                                                                       int32_t* counts) {
+  __shared__ int part[kSsThreads / kWave];
+  const int w = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
+  const int v = s * (e.nb + 1) + w;
+  const int n = num[s], goff = ioff ? ioff[s] : 0;
+  int before = 0;
+  for (int r = 0; r < kSsPer; ++r) {
+    if (r * kSsThreads >= n) break;
+    const int i = r * kSsThreads + t;
+    const bool f = i < n && ib_class(lab_in[(int64_t)s * lstride + i], iou + (int64_t)s * istride, (int64_t)i - goff, e) == w;
+    int tt;
+    const int rk = block_rank(f, part, &tt);
+    if (f) lists[(int64_t)v * ld + before + rk] = i;
+    before += tt;
+  }
+  if (t == 0) counts[v] = before;
+}
+
 int32_t launch_compact_lists(int32_t S, const int64_t* labels, int64_t label_seg_stride,
                              const int32_t* num, int64_t max_n, int npred, const int* preds,
                              int32_t** lists, int64_t list_seg_stride, int32_t* counts,
@@ -993,6 +1157,66 @@ extern "C" int32_t frh_sample_random(int32_t num_segs, const int64_t* labels_in,
                                      void* stream) {
   return frh::sample_random_impl(num_segs, labels_in, label_seg_stride, num_boxes, max_boxes, max_num, pos_num, seed,
                                  labels_out, sel, sel_counts, status, workspace, ws_bytes, stream, false);
+}
+
+static int32_t ib_edges(int32_t num_bins, const float* bin_lo, const float* bin_hi, IbEdges* e) {
+  FRH_REQUIRE(num_bins >= 1 && num_bins <= kIbMaxBins, "num_bins must be in [1, %d]", kIbMaxBins);
+  FRH_REQUIRE(bin_lo && bin_hi, "null bin edges");
+  for (int j = 0; j + 1 < num_bins; ++j)
+    FRH_REQUIRE(bin_hi[j] <= bin_lo[j + 1], "IoU bins %d and %d overlap", j, j + 1);
+  *e = IbEdges{};
+  e->nb = num_bins;
+  for (int j = 0; j < num_bins; ++j) e->lo[j] = bin_lo[num_bins - 1 - j], e->hi[j] = bin_hi[num_bins - 1 - j];
+  return FRH_OK;
+}
+
+extern "C" int32_t frh_sample_iou_balanced(int32_t num_segs, const int64_t* labels_in, int64_t label_seg_stride,
+                                           const float* ious, int64_t iou_seg_stride, const int32_t* iou_offsets,
+                                           const int32_t* num_boxes, int64_t max_boxes, int32_t max_num, int32_t pos_num, int32_t num_bins,
+                                           const float* bin_lo, const float* bin_hi, uint64_t seed,
+                                           int64_t* labels_out, int32_t* sel, int32_t* sel_counts, void* stream) {
+  FRH_REQUIRE(num_segs >= 0 && max_boxes >= 0, "negative sizes");
+  FRH_REQUIRE(num_segs <= 65535, "too many segments");
+  FRH_REQUIRE(pos_num <= max_num && pos_num >= 0, "pos_num must be in [0, max_num]");
+  IbEdges e;
+  const int32_t st = ib_edges(num_bins, bin_lo, bin_hi, &e);
+  if (st != FRH_OK) return st;
+  if (num_segs == 0 || max_boxes == 0) return FRH_OK;
+  FRH_REQUIRE(labels_in && ious && num_boxes && (labels_out || sel), "null pointer argument");
+  FRH_REQUIRE(!sel == !sel_counts, "sel and sel_counts go together");
+  FRH_REQUIRE(labels_in != labels_out, "labels_out must not alias labels_in");
+  if (max_boxes > kSsMax) {
+    set_error("frh_sample_iou_balanced: %lld rows per image exceed the one-workgroup capacity %d",
+              (long long)max_boxes, kSsMax);
+    return FRH_EUNSUPPORTED;
+  }
+  hipLaunchKernelGGL(sampler_iou_kernel, dim3((unsigned)(1 + num_bins), (unsigned)num_segs), dim3(kSsThreads), 0,
+                     as_stream(stream), labels_in, label_seg_stride, ious, iou_seg_stride, iou_offsets, num_boxes, max_num,
+                     pos_num, seed, e, labels_out, sel, (int64_t)(max_num > 0 ? max_num : 1), sel_counts);
+  return check_launch("frh_sample_iou_balanced");
+}
+
+extern "C" int32_t frh_sample_iou_candidates(int32_t num_segs, const int64_t* labels, int64_t label_seg_stride,
+                                             const float* ious, int64_t iou_seg_stride, const int32_t* iou_offsets,
+                                             const int32_t* num_boxes, int64_t max_boxes, int32_t num_bins, const float* bin_lo,
+                                             const float* bin_hi, int32_t* lists, int64_t list_ld, int32_t* counts,
+                                             void* stream) {
+  FRH_REQUIRE(num_segs >= 0 && num_segs <= 65535 && max_boxes >= 0, "bad sizes");
+  IbEdges e;
+  const int32_t st = ib_edges(num_bins, bin_lo, bin_hi, &e);
+  if (st != FRH_OK) return st;
+  if (num_segs == 0) return FRH_OK;
+  FRH_REQUIRE(labels && ious && num_boxes && lists && counts, "null pointer argument");
+  FRH_REQUIRE(list_ld >= max_boxes, "list_ld must hold max_boxes rows");
+  if (max_boxes > kSsMax) {
+    set_error("frh_sample_iou_candidates: %lld rows per image exceed the one-workgroup capacity %d",
+              (long long)max_boxes, kSsMax);
+    return FRH_EUNSUPPORTED;
+  }
+  hipLaunchKernelGGL(sampler_iou_lists_kernel, dim3((unsigned)(1 + num_bins), (unsigned)num_segs), dim3(kSsThreads), 0,
+                     as_stream(stream), labels, label_seg_stride, ious, iou_seg_stride, iou_offsets, num_boxes, e, lists,
+                     list_ld, counts);
+  return check_launch("frh_sample_iou_candidates");
 }
 
 // two_launches: the keys + collect launches even where the one-launch sampler applies

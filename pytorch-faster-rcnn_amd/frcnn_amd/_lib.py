@@ -38,6 +38,10 @@ SIGNATURES = {
                                  c_vp, c_vp]),
     'frh_sample_random': (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_size, c_vp]),
+    'frh_sample_iou_balanced': (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                        P(c_f32), P(c_f32), c_u64, c_vp, c_vp, c_vp, c_vp]),
+    'frh_sample_iou_candidates': (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, P(c_f32),
+                                          P(c_f32), c_vp, c_i64, c_vp, c_vp]),
     'frh_anchor_target_workspace': (c_size, [c_i32, c_i64]),
     'frh_anchor_target': (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
                                   c_vp, c_i64, P(c_f32), P(c_f32), c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -100,6 +104,11 @@ SIGNATURES = {
     'frh_bn_act_maxpool': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'frh_loss_workspace': (c_size, []),
     'frh_fpn_merge_nhwc': (c_i32, [c_vp, P(c_i64), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    'frh_bfp_argmax_elems': (c_size, [c_i32, c_i32, c_i32, c_i32, P(c_i32)]),
+    'frh_bfp_fwd': (c_i32, [c_i32, c_i32, c_i32, c_i32, P(c_vp), P(c_i32), P(c_i64), c_vp, P(c_vp), c_vp, c_i64,
+                            c_vp]),
+    'frh_bfp_bwd': (c_i32, [c_i32, c_i32, c_i32, c_i32, P(c_vp), P(c_i32), P(c_i64), c_vp, c_i64, c_vp, P(c_vp),
+                            c_vp]),
     'frh_bias_act_nhwc': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     'frh_image_preprocess': (c_i32, [c_vp, c_i32, P(c_i64), P(c_i32), P(c_i32), P(c_i32), P(c_f32), P(c_f32), c_i32,
                                      c_vp, c_i32, c_i32, c_vp]),
@@ -111,6 +120,10 @@ SIGNATURES = {
                                   c_vp, c_vp, c_vp, c_size, c_vp]),
     'frh_smooth_l1_bwd': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32,
                                   c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    'frh_balanced_l1_fwd': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32,
+                                    c_f32, c_f32, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'frh_balanced_l1_bwd': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32,
+                                    c_f32, c_f32, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     'frh_det_loss_fwd': (c_i32, [c_i32, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32,
                                  c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32,
                                  c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),

@@ -51,12 +51,17 @@ def bbox_targets_batched(props_list, gt_bboxes, gt_labels, assigner, sampler, ta
     props, pstride, pcount, pmax = _as_batch(props_list, dev)
     gts, gcnt, gmax = ops.pack_boxes([g.float() for g in gt_bboxes], dev)
     glab = ops.pack_labels(gt_labels, gmax, dev)
-    labels, _ = ops.maxiou_assign(props, pstride, pcount, pmax, gts, gcnt, gmax, assigner.pos_iou, assigner.neg_iou,
-                                  assigner.min_pos_iou, num_segs=S)
+    labels, max_iou = ops.maxiou_assign(props, pstride, pcount, pmax, gts, gcnt, gmax, assigner.pos_iou,
+                                        assigner.neg_iou, assigner.min_pos_iou, num_segs=S)
     max_rows = gmax + pmax
     rows, num_rows = ops.prepend_gt_labels(labels, pcount, gcnt, max_rows)
-    rows = ops.sample_labels(rows, num_rows, max_rows, sampler.max_num, sampler.pos_num,
-                             lists=ops.sampler_mode() == 'device')
+    if getattr(sampler, 'needs_iou', False):
+        # the assigner's IoU of row i sits gcnt rows earlier (the prepended gts are positives: never read)
+        rows = sampler.sample(rows, max_iou, num_rows, max_rows, iou_offsets=gcnt,
+                              lists=ops.sampler_mode() == 'device')
+    else:
+        rows = ops.sample_labels(rows, num_rows, max_rows, sampler.max_num, sampler.pos_num,
+                                 lists=ops.sampler_mode() == 'device')
     r = ops.bbox_target_batched(rows, num_rows, gcnt, max_rows, props, pstride, gts, glab,
                                 target_means, target_stds, sampler.max_num, sync=sync)
     if not sync:

@@ -8,9 +8,9 @@ import copy
 from torch.optim import SGD
 
 from .backbones import ResNet, ResLayerC5
-from .necks import FPN
-from .region import MaxIoUAssigner, RandomSampler, BasicRoIExtractor
-from .losses import (FocalLoss, SmoothL1Loss, CrossEntropyLoss, GIoULoss, IoULoss, QualityFocalLoss,
+from .necks import FPN, BFP
+from .region import MaxIoUAssigner, RandomSampler, IoUBalancedNegSampler, BasicRoIExtractor
+from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, CrossEntropyLoss, GIoULoss, IoULoss, QualityFocalLoss,
                      DistributionFocalLoss)
 from .heads import RPNHead, RCNNHead, RetinaHead, FCOSHead
 from .detectors import CascadeRCNN, RetinaNet, FCOS
@@ -18,7 +18,8 @@ from .ops import RoIAlign, RoIPool
 
 _MODULE_LIST = [RetinaNet, CascadeRCNN, FCOS, ResNet, ResLayerC5, FPN, RetinaHead, RPNHead, RCNNHead, FCOSHead,
                 CrossEntropyLoss, SmoothL1Loss, FocalLoss, GIoULoss, IoULoss, QualityFocalLoss, DistributionFocalLoss,
-                BasicRoIExtractor, RoIAlign, RoIPool, SGD, MaxIoUAssigner, RandomSampler]
+                BasicRoIExtractor, RoIAlign, RoIPool, SGD, MaxIoUAssigner, RandomSampler, BFP, IoUBalancedNegSampler,
+                BalancedL1Loss]
 
 MODULES = {cls.__name__: cls for cls in _MODULE_LIST}
 

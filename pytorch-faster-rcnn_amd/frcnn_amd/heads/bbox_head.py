@@ -69,7 +69,7 @@ class BBoxHead(nn.Module):
             if fused is not None:
                 return fused
             cls_loss = self.loss_cls(cls_out, tar_label) / avg_factor
-            if isinstance(self.loss_bbox, losses.SmoothL1Loss):
+            if isinstance(self.loss_bbox, (losses.SmoothL1Loss, losses.BalancedL1Loss)):
                 # fused class selection + positive-row mask + smooth-L1 (one kernel each way)
                 if self.reg_class_agnostic:
                     reg_loss = self.loss_bbox.masked(reg_out, tar_param.t(), tar_label, rows_dim=0)

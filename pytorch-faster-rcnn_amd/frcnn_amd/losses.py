@@ -8,6 +8,7 @@ numerics reference of the GPU tests.  Semantics follow the reference, including
 its quirk that FocalLoss ignores the configured alpha/gamma/loss_weight
 (losses.py:106-109).
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -91,6 +92,57 @@ class SmoothL1Loss(nn.Module):
         """bbox_head.py:70-76: the labelled class's deltas of reg_out [n, 4*C] at the positive rows."""
         if reg_out.is_cuda:
             return self.loss_weight * ops.smooth_l1_class_select(reg_out, num_classes, target, label, self.beta)
+        n = len(label)
+        sel = reg_out.view(-1, 4, num_classes)[torch.arange(n), :, label]
+        return self.masked(sel, target, label, 0)
+
+
+def balanced_l1_loss(pred, target, beta=1.0, alpha=0.5, gamma=1.5):
+    """losses.py:158-168 (elementwise; borrowed from mmdet by the reference)."""
+    if pred.size() != target.size():
+        raise AssertionError('balanced_l1_loss: shape mismatch')
+    diff = torch.abs(pred - target)
+    b = np.e ** (gamma / alpha) - 1
+    return torch.where(diff < beta,
+                       alpha / b * (b * diff + 1) * torch.log(b * diff / beta + 1) - alpha * diff,
+                       gamma * diff + gamma / b - alpha * beta)
+
+
+def balanced_l1_slope(d, beta=1.0, alpha=0.5, gamma=1.5):
+    """d/dd of the balanced-L1 element at d = |pred - target| (what the HIP backward
+    multiplies by sign(pred - target)): alpha log(b d / beta + 1) + alpha (b d + 1) / (b d + beta)
+    - alpha below beta, gamma from beta on."""
+    b = np.e ** (gamma / alpha) - 1
+    return torch.where(d < beta, alpha * torch.log(b * d / beta + 1) + alpha * (b * d + 1) / (b * d + beta) - alpha,
+                       torch.full_like(d, gamma))
+
+
+class BalancedL1Loss(nn.Module):
+    """losses.py:170-180; the HIP forms mirror SmoothL1Loss's (plain, masked, class-selected)."""
+
+    def __init__(self, alpha=0.5, gamma=1.5, beta=1.0, loss_weight=1.0):
+        super().__init__()
+        self.alpha, self.gamma, self.beta, self.loss_weight = alpha, gamma, beta, loss_weight
+
+    def _cpu(self, x, y):
+        return balanced_l1_loss(x, y, beta=self.beta, alpha=self.alpha, gamma=self.gamma).sum()
+
+    def forward(self, pred, label):
+        if pred.is_cuda and pred.dim() == 2:
+            return self.loss_weight * ops.balanced_l1_loss(pred, label, self.beta, self.alpha, self.gamma)
+        return self._cpu(pred, label) * self.loss_weight
+
+    def masked(self, x, y, label, rows_dim=0):
+        if x.is_cuda:
+            return self.loss_weight * ops.balanced_l1_loss(x, y, self.beta, self.alpha, self.gamma, label, rows_dim)
+        m = (label > 0).view(-1, 1) if rows_dim == 0 else (label > 0).view(1, -1)
+        z = x.new_zeros(())
+        return self.loss_weight * self._cpu(torch.where(m, x, z), torch.where(m, y, z))
+
+    def class_selected(self, reg_out, num_classes, target, label):
+        if reg_out.is_cuda:
+            return self.loss_weight * ops.balanced_l1_class_select(reg_out, num_classes, target, label, self.beta,
+                                                                   self.alpha, self.gamma)
         n = len(label)
         sel = reg_out.view(-1, 4, num_classes)[torch.arange(n), :, label]
         return self.masked(sel, target, label, 0)

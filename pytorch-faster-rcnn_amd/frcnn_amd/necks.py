@@ -1,4 +1,4 @@
-"""FPN neck (convolutions on PyTorch-ROCm).
+"""FPN neck (convolutions on PyTorch-ROCm) and the BFP neck after it (HIP, no parameters).
 
 Same topology and parameter names as the reference FPN (`lib/necks.py:7-90`):
 1x1 laterals, top-down nearest upsample-add, 3x3 output convs, and extra
@@ -14,12 +14,84 @@ in MIOpen's NHWC layout (channels-last weights, `utils.ChannelsLastConvs`) --
 directly (strided kernels, the channel-quad RoIAlign).  CPU tensors take the
 reference's NCHW ops.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from .utils import ChannelsLastConvs
 from . import ops
+
+
+def adaptive_window(o, n_in, n_out):
+    """Input cells [start, end) of adaptive-pool output o (torch's rule; csrc/bfp.hip pool_start / pool_end)."""
+    return (o * n_in) // n_out, ((o + 1) * n_in + n_out - 1) // n_out
+
+
+def adaptive_windows_of(p, n_in, n_out):
+    """Outputs [first, last] of an adaptive pool n_in -> n_out whose window holds input cell p
+    (csrc/bfp.hip win_first / win_last: the backward's gather)."""
+    return (p * n_out) // n_in, min(((p + 1) * n_out - 1) // n_in, n_out - 1)
+
+
+def nearest_source(d, n_in, n_out):
+    """Source cell of destination d of a nearest resize n_in -> n_out (torch's rule in f32;
+    csrc/bfp.hip nearest_of)."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    return min(int(np.floor(np.float32(d) * scale)), n_in - 1)
+
+
+class BFP(nn.Module):
+    """Balanced feature pyramid of Libra R-CNN, refine_type=None (reference lib/necks.py:93-141):
+    every level is resampled to the refine level's size (adaptive max pool from the finer
+    levels, nearest from the coarser ones), the others' mean is the refine map, and each
+    level gets it back resampled to its own size as a residual.  No parameters.
+
+    On a HIP device the whole neck is two launches forward and two backward
+    (`ops.bfp`, csrc/bfp.hip) over levels of any layout, written channels-last; CPU tensors
+    take the reference's torch ops."""
+
+    def __init__(self, in_channels=256, num_levels=5, refine_level=2, refine_type=None):
+        super().__init__()
+        if refine_type not in [None]:
+            raise AssertionError('refine_type must be None')
+        if not 0 <= refine_level < num_levels:
+            raise AssertionError('refine_level out of range')
+        self.in_channels = in_channels
+        self.num_levels = num_levels
+        self.refine_level = refine_level
+        self.refine_type = None
+
+    def init_layers(self):
+        pass
+
+    def init_weights(self):
+        pass
+
+    def forward(self, feats):
+        if len(feats) != self.num_levels:
+            raise AssertionError('BFP expects {} levels'.format(self.num_levels))
+        if feats[0].is_cuda and feats[0].dtype == torch.float32:
+            return ops.bfp(feats, self.refine_level)
+        r = self.refine_level
+        size = feats[r].shape[-2:]
+        uniform = []
+        for i in range(self.num_levels):
+            if i < r:
+                uniform.append(F.adaptive_max_pool2d(feats[i], output_size=size))
+            elif i > r:
+                uniform.append(F.interpolate(feats[i], size=size, mode='nearest'))
+        refine = sum(uniform) / len(uniform)
+        outs = []
+        for i in range(self.num_levels):
+            if i < r:
+                residual = F.interpolate(refine, size=feats[i].shape[-2:], mode='nearest')
+            elif i > r:
+                residual = F.adaptive_max_pool2d(refine, output_size=feats[i].shape[-2:])
+            else:
+                residual = refine
+            outs.append(feats[i] + residual)
+        return outs
 
 
 class FPN(ChannelsLastConvs):

@@ -354,6 +354,81 @@ def _numpy_keep(n, cap):
     return np.sort(perm[n - cap:]).astype(np.int32)
 
 
+def _numpy_first(n, cap):
+    """List positions kept by the reference's `np.random.choice(n, cap, replace=False)`
+    (utils.random_select: permutation(n)[:cap], the FIRST cap of the permutation), drawn
+    only when the class holds more than its quota (region.py:145,159)."""
+    if n <= cap:
+        return np.arange(n, dtype=np.int32)
+    return np.random.permutation(n)[:cap].astype(np.int32)
+
+
+def iou_bin_quotas(npos, bin_counts, max_num, pos_num):
+    """region.py:145-161: (kept positives, kept negatives per bin in visiting order, highest
+    bin first) from the class counts."""
+    kp = min(int(npos), pos_num)
+    num_neg = max_num - kp
+    nb = len(bin_counts)
+    per_bin = int(num_neg / nb)
+    chosen, takes = 0, []
+    for j, c in enumerate(bin_counts):
+        allowed = per_bin if j < nb - 1 else num_neg - chosen
+        takes.append(min(int(c), allowed))
+        chosen += takes[-1]
+    return kp, takes
+
+
+def sample_iou_balanced(labels, ious, num_boxes, max_boxes, max_num, pos_num, bin_lo, bin_hi, iou_offsets=None,
+                        mode=None, lists=False):
+    """Batched IoUBalancedNegSampler over labels [S, >=max_boxes] (region.py:128-172); row i of
+    image s has IoU ious[s, i - iou_offsets[s]] (read for negatives only).  bin_lo / bin_hi:
+    the f32 bin edges, ascending.  Returns as sample_labels: the sampled labels (rows past an
+    image's count are not written), or with lists=True (device mode) a SampleLists whose
+    negatives' list holds every bin's choices."""
+    mode = mode or _SAMPLER['mode']
+    _need_cuda(labels, ious, num_boxes, iou_offsets)
+    if ious.dtype != torch.float32 or ious.stride(-1) != 1 or labels.stride(-1) != 1:
+        raise AssertionError('sample_iou_balanced: f32 IoUs and labels with contiguous rows')
+    S = labels.shape[0]
+    dev = labels.device
+    nb = len(bin_lo)
+    lo, hi = f32_array(bin_lo), f32_array(bin_hi)
+    if mode == 'device':
+        _SAMPLER['calls'] += 1
+        seed = (_SAMPLER['seed'] * 0x9E3779B97F4A7C15 + _SAMPLER['calls']) & 0xFFFFFFFFFFFFFFFF
+        out = None if lists else torch.empty_like(labels)
+        sel = torch.empty(S, 2, max(int(max_num), 1), dtype=torch.int32, device=dev) if lists else None
+        sel_cnt = torch.empty(S, 2, dtype=torch.int32, device=dev) if lists else None
+        call('frh_sample_iou_balanced', S, ptr(labels), labels.stride(0), ptr(ious), ious.stride(0), ptr(iou_offsets),
+             ptr(num_boxes), max_boxes, int(max_num), int(pos_num), nb, lo, hi, seed, ptr(out), ptr(sel), ptr(sel_cnt),
+             stream_of(labels))
+        return SampleLists(labels, sel, sel_cnt, max_num) if lists else out
+    out = torch.empty_like(labels)
+    ld = max(max_boxes, 1)
+    cand = torch.empty(S, 1 + nb, ld, dtype=torch.int32, device=dev)
+    counts = torch.empty(S, 1 + nb, dtype=torch.int32, device=dev)
+    call('frh_sample_iou_candidates', S, ptr(labels), labels.stride(0), ptr(ious), ious.stride(0), ptr(iou_offsets),
+         ptr(num_boxes), max_boxes, nb, lo, hi, ptr(cand), ld, ptr(counts), stream_of(labels))
+    cnt = counts.cpu().numpy()  # the one host round trip, as ops.sample_labels
+    check_device_status(dev)
+    keep_ld = max(int(max_num), 1)
+    keep = np.zeros((2, S, keep_ld), dtype=np.int32)
+    kc = np.zeros((S, 2), dtype=np.int32)
+    for s in range(S):  # draw order: positives, then the bins from the highest down, image by image
+        _, takes = iou_bin_quotas(cnt[s, 0], cnt[s, 1:], max_num, pos_num)
+        kp = _numpy_first(int(cnt[s, 0]), pos_num)
+        kneg = [_numpy_first(int(cnt[s, 1 + j]), takes[j]) + j * ld for j in range(nb)]
+        kneg = np.concatenate(kneg).astype(np.int32)
+        kc[s, 0], kc[s, 1] = len(kp), len(kneg)
+        keep[0, s, :len(kp)] = kp
+        keep[1, s, :len(kneg)] = kneg
+    keep_t = torch.from_numpy(keep).to(dev)
+    kc_t = torch.from_numpy(kc).to(dev)
+    call('frh_sample_apply', S, ptr(labels), labels.stride(0), ptr(num_boxes), max_boxes, ptr(cand), ptr(cand[:, 1:]),
+         (1 + nb) * ld, ptr(keep_t[0]), ptr(keep_t[1]), keep_ld, ptr(kc_t), ptr(out), stream_of(labels))
+    return out
+
+
 # ---------------------------------------------------------------- target gathers (a6/a12)
 def anchor_target_batched(labels, num_boxes, max_boxes, anchors, gts, gt_labels, means, stds, max_out_per_seg,
                           sync=True):
@@ -994,6 +1069,70 @@ def fpn_merge_nhwc(lat, up=None, bias=None):
     return _FpnMerge.apply(lat, up, bias)
 
 
+# ---------------------------------------------------------------- BFP neck (Libra R-CNN)
+def _nhwc_empty(shape, dev):
+    return torch.empty(tuple(shape), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+
+
+def _ptrs_or_null(ts):
+    return (_lib.c_vp * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+class _Bfp(torch.autograd.Function):
+    """BFP.forward (lib/necks.py:116-141) as two launches (frh_bfp_fwd), channels-last outputs;
+    backward two launches (frh_bfp_bwd) from the argmax cells the forward stored."""
+
+    @staticmethod
+    def forward(ctx, refine_level, *feats):
+        L = len(feats)
+        B, C = int(feats[0].shape[0]), int(feats[0].shape[1])
+        dev = feats[0].device
+        hw = [int(v) for f in feats for v in f.shape[2:]]
+        outs = [_nhwc_empty(f.shape, dev) for f in feats]
+        refine = torch.empty(B, hw[2 * refine_level], hw[2 * refine_level + 1], C, dtype=torch.float32, device=dev)
+        amax, n_arg = None, 0
+        if any(ctx.needs_input_grad[1:]):
+            n_arg = int(_lib.query('frh_bfp_argmax_elems', L, refine_level, B, C, i32_array(hw)))
+            amax = torch.empty(max(n_arg, 1), dtype=torch.int32, device=dev)
+        call('frh_bfp_fwd', L, refine_level, B, C, ptr_array(feats), i32_array(hw),
+             i64_array([s for f in feats for s in f.stride()]), ptr(refine), ptr_array(outs), ptr(amax), n_arg,
+             stream_of(feats[0]))
+        ctx.cfg = (refine_level, hw, B, C, n_arg)
+        if amax is not None:
+            ctx.save_for_backward(amax)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        r, hw, B, C, n_arg = ctx.cfg
+        (amax,) = ctx.saved_tensors
+        dev = amax.device
+        L = len(gouts)
+        gs = [_f32(g) if g is not None else
+              torch.zeros(B, C, hw[2 * i], hw[2 * i + 1], dtype=torch.float32, device=dev).contiguous(
+                  memory_format=torch.channels_last) for i, g in enumerate(gouts)]
+        gins = [None if i == r else _nhwc_empty((B, C, hw[2 * i], hw[2 * i + 1]), dev) for i in range(L)]
+        gref = torch.empty(B, hw[2 * r], hw[2 * r + 1], C, dtype=torch.float32, device=dev)
+        call('frh_bfp_bwd', L, r, B, C, ptr_array(gs), i32_array(hw), i64_array([s for g in gs for s in g.stride()]),
+             ptr(amax), n_arg, ptr(gref), _ptrs_or_null(gins), stream_of(amax))
+        gins[r] = gs[r]  # out[r] = feats[r] + refine, and refine does not depend on feats[r]
+        return (None,) + tuple(gins)
+
+
+def bfp(feats, refine_level):
+    """The BFP neck's forward (lib/necks.py:116-141, refine_type=None) on f32 HIP levels of any
+    layout; returns channels-last levels."""
+    feats = list(feats)
+    _need_cuda(*feats)
+    if not 2 <= len(feats) <= 8 or not 0 <= refine_level < len(feats):
+        raise AssertionError('bfp: 2..8 levels and a refine_level among them')
+    b, c = feats[0].shape[:2]
+    for f in feats:
+        if f.dim() != 4 or f.dtype != torch.float32 or f.shape[0] != b or f.shape[1] != c or f.device != feats[0].device:
+            raise AssertionError('bfp: f32 [B, C, H, W] levels of one batch, channel count and device')
+    return list(_Bfp.apply(int(refine_level), *feats))
+
+
 class _BiasAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, bias, relu):
@@ -1207,6 +1346,43 @@ def smooth_l1_class_select(reg_out, num_classes, target, label, beta):
     """BBoxHead's regression loss: reg_out [n, 4*C] viewed [n, 4, C], the labelled class's
     deltas of the positive rows against target [n, 4] (any strides), summed."""
     return _SmoothL1.apply(*_l1_class_select_args(reg_out, num_classes, target, label), beta)
+
+
+class _BalancedL1(torch.autograd.Function):
+    """_SmoothL1 with the balanced-L1 element (frh_balanced_l1_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, y, label, xs, ys, n, m, n_sel, beta, alpha, gamma):
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = _loss_workspace(x)
+        call('frh_balanced_l1_fwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
+             float(beta), float(alpha), float(gamma), ptr(status_word(x.device)), ptr(out), ptr(ws), ws.numel(),
+             stream_of(x))
+        ctx.save_for_backward(x, y, label)
+        ctx.cfg = (xs, ys, n, m, n_sel, beta, alpha, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, label = ctx.saved_tensors
+        xs, ys, n, m, n_sel, beta, alpha, gamma = ctx.cfg
+        gx = torch.zeros_like(x)
+        if gx.stride() != x.stride():
+            raise AssertionError('balanced_l1: gradient layout differs from the input')
+        g = _f32(g).contiguous()
+        call('frh_balanced_l1_bwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
+             float(beta), float(alpha), float(gamma), ptr(g), ptr(gx), xs[0], xs[1], xs[2], stream_of(x))
+        return (gx,) + (None,) * 10
+
+
+def balanced_l1_loss(x, y, beta, alpha, gamma, label=None, rows_dim=0):
+    """Summed balanced_l1_loss (lib/losses.py:158-168) of x and y, as smooth_l1_loss."""
+    return _BalancedL1.apply(*_l1_args(x, y, label, rows_dim), beta, alpha, gamma)
+
+
+def balanced_l1_class_select(reg_out, num_classes, target, label, beta, alpha, gamma):
+    """smooth_l1_class_select with the balanced-L1 element."""
+    return _BalancedL1.apply(*_l1_class_select_args(reg_out, num_classes, target, label), beta, alpha, gamma)
 
 
 class _DetLoss(torch.autograd.Function):

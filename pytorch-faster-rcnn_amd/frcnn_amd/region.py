@@ -1,5 +1,6 @@
 """Masks, MaxIoU assignment, random sampling and the FPN RoI extractor
 (reference lib/region.py) on the HIP kernels."""
+import numpy as np
 import torch
 from torch import nn
 
@@ -80,6 +81,62 @@ class RandomSampler(object):
         n = labels.numel()
         num = torch.tensor([n], dtype=torch.int32, device=labels.device)
         out = ops.sample_labels(labels.view(1, n).long(), num, n, self.max_num, self.pos_num)
+        return out.view(-1).to(labels.dtype)
+
+
+def _f32_threshold(v):
+    """The f32 value torch compares an f32 tensor against when the other operand is the Python
+    float v: the scalar is cast to the tensor's dtype, i.e. rounded to the nearest f32 (so
+    `x >= 0.7` holds for x = float32(0.7) < 0.7)."""
+    return float(np.float32(v))
+
+
+class IoUBalancedNegSampler(object):
+    """region.py:128-172: keep <= pos_num positives, then fill the negatives bin by bin of
+    their IoU, from the highest bin down (floor_thr / floor_fraction accepted and ignored, as
+    in the reference).  Deviation: bin edges that overlap after rounding to f32, where the
+    reference would count a box in two bins, raise ValueError."""
+    needs_iou = True
+
+    def __init__(self, max_num, pos_num, num_bins=3, max_iou=0.5, floor_thr=-1, floor_fraction=0):
+        if max_num < pos_num:
+            raise AssertionError('pos_num > max_num')
+        if not 0 < max_iou <= 1:
+            raise AssertionError('max_iou must be in (0, 1]')
+        if not 1 <= num_bins <= 8:
+            raise AssertionError('num_bins must be in [1, 8]')
+        self.max_num = max_num
+        self.pos_num = pos_num
+        self.num_bins = num_bins
+        self.max_iou = max_iou
+        self.bin_lo, self.bin_hi = self.bin_edges()
+
+    def bin_edges(self):
+        """f32 (lo, hi) per bin, ascending, from the reference's own expressions
+        (region.py:150-152)."""
+        bin_size = self.max_iou / self.num_bins
+        starts = [i * bin_size for i in range(self.num_bins)]
+        ends = [s + bin_size for s in starts]
+        lo, hi = [_f32_threshold(s) for s in starts], [_f32_threshold(e) for e in ends]
+        self.check_bins(lo, hi)
+        return lo, hi
+
+    @staticmethod
+    def check_bins(lo, hi):
+        for j in range(len(lo) - 1):
+            if hi[j] > lo[j + 1]:
+                raise ValueError('IoUBalancedNegSampler: bins {} and {} overlap'.format(j, j + 1))
+
+    def sample(self, labels, ious, num_boxes, max_boxes, iou_offsets=None, lists=False):
+        """Batched form: labels [S, >= max_boxes], row i of image s having IoU
+        ious[s, i - iou_offsets[s]]."""
+        return ops.sample_iou_balanced(labels, ious, num_boxes, max_boxes, self.max_num, self.pos_num, self.bin_lo,
+                                       self.bin_hi, iou_offsets, lists=lists)
+
+    def __call__(self, labels, overlaps, props_bbox=None, gt_bbox=None):
+        n = labels.numel()
+        num = torch.tensor([n], dtype=torch.int32, device=labels.device)
+        out = self.sample(labels.view(1, n).long(), overlaps.float().contiguous().view(1, n), num, n)
         return out.view(-1).to(labels.dtype)
 
 
