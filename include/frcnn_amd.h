@@ -524,6 +524,20 @@ int32_t frh_bn_act(const float* x, const float* skip, float* y, const float* gam
 int32_t frh_bn_act_maxpool(const float* x, float* y, const float* gamma, const float* beta, const float* mean,
                            const float* var, float eps, int64_t n, int32_t c, int32_t h, int32_t w, void* stream);
 
+/* A bottleneck's 1x1 / stride-1 convolution with the frh_bn_act epilogue on the accumulator
+ * (torchvision Bottleneck.forward: conv1 / conv3 / the stride-1 projection, each followed by
+ * its frozen BN): y[n, co, p] = act((sum_ci w[co, ci] * x[n, ci, p]) * s[co] + b[co]
+ * (+ skip[n, co, p])), s and b as in frh_bn_act; the raw conv output is never written.
+ * x [n, cin, hw], skip / y [n, cout, hw] contiguous NCHW f32, w [cout, cin] contiguous, all
+ * 16-byte aligned; hw % 4 == 0, cin % 16 == 0, cout % 64 == 0 (anything else: FRH_EINVAL);
+ * gamma / beta may be NULL (1 / 0); mean == var == NULL: no BN (the raw convolution, plus
+ * skip, plus ReLU); y must not alias x or skip.  One launch, no workspace.  The sum over ci
+ * is an exact-f32 fmaf chain (f32 MFMA) in a fixed order: the same inputs give the same bits
+ * on every launch, and given the same accumulator the epilogue gives frh_bn_act's bits. */
+int32_t frh_conv1x1_bn_act(const float* x, const float* w, const float* skip, float* y, const float* gamma,
+                           const float* beta, const float* mean, const float* var, float eps, int64_t n,
+                           int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream);
+
 /* FPN top-down merge into channels-last levels (lib/necks.py:72-84):
  * out[b, y, x, c] = (lat[b, c, y, x] + bias[c]) + up[b, iy, ix, c] with torch's nearest rule
  * (iy = min(floor(y * (float)up_h / height), up_h - 1); y / 2 when height == 2 * up_h);

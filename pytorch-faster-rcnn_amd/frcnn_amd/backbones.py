@@ -16,7 +16,7 @@ import logging
 import torch
 from torch import nn
 
-from .ops import bn_act, bn_act_maxpool
+from .ops import bn_act, bn_act_maxpool, conv1x1_bn_act
 
 # blocks per stage for each depth
 _STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -44,11 +44,13 @@ class Bottleneck(nn.Module):
             self.downsample = nn.Sequential(*_conv_bn(in_channels, out_channels, 1, stride=stride))
 
     def forward(self, x):
-        # frozen BN (+ residual) + ReLU as one HIP epilogue pass per conv (ops.bn_act)
-        y = bn_act(self.conv1(x), self.bn1)
+        # frozen BN (+ residual) + ReLU: inside the 1x1 convs' HIP GEMM where nothing needs a
+        # gradient (ops.conv1x1_bn_act; the stride-2 projections and every training path fall
+        # through to conv + ops.bn_act), one HIP epilogue pass after the 3x3 conv (ops.bn_act)
+        y = conv1x1_bn_act(self.conv1, self.bn1, x)
         y = bn_act(self.conv2(y), self.bn2)
-        skip = bn_act(self.downsample[0](x), self.downsample[1], relu=False) if self.do_downsample else x
-        return bn_act(self.conv3(y), self.bn3, skip=skip)
+        skip = conv1x1_bn_act(self.downsample[0], self.downsample[1], x, relu=False) if self.do_downsample else x
+        return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip)
 
 
 class ResNet(nn.Module):

@@ -1211,6 +1211,49 @@ def bn_act(x, bn, skip=None, relu=True):
     return _FrozenBNAct.apply(x, skip, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+# Channel classes (cin, cout) at which tools/bench_conv1x1.py measured frh_conv1x1_bn_act slower
+# than MIOpen / Tensile's 1x1 conv followed by frh_bn_act (the long-sum reductions of stages
+# 2 to 4; both times in DESIGN section 4): they keep that path.
+_CONV1X1_EXCLUDED = frozenset([(512, 128), (512, 256), (1024, 256), (1024, 512), (2048, 512)])
+
+
+def conv1x1_fused_ok(conv, bn, x, skip=None):
+    """Whether conv1x1_bn_act takes the fused HIP entry for these arguments."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+            and not bn.training and conv.bias is None and conv.weight.dtype == torch.float32
+            and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.weight.is_contiguous()):
+        return False
+    cout, cin, hw = conv.out_channels, conv.in_channels, x.shape[2] * x.shape[3]
+    if x.shape[1] != cin or hw % 4 or cin % 16 or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16 \
+            or (cin, cout) in _CONV1X1_EXCLUDED:
+        return False
+    if skip is not None and not (skip.is_cuda and skip.dtype == torch.float32 and skip.is_contiguous()
+                                 and skip.shape == (x.shape[0], cout, x.shape[2], x.shape[3])
+                                 and skip.data_ptr() % 16 == 0):
+        return False
+    return not _needs_grad(x, skip, conv.weight, bn.weight, bn.bias)
+
+
+def conv1x1_bn_act(conv, bn, x, skip=None, relu=True):
+    """act(bn(conv(x)) (+ skip)) for a bottleneck's 1x1 / stride-1 conv and its eval-mode BN in
+    one HIP launch (frh_conv1x1_bn_act: the BN / residual / ReLU epilogue on the GEMM's
+    accumulator, no raw conv output in HBM) when nothing needs a gradient through it (the graphed
+    trunk, inference, frozen stages); otherwise bn_act(conv(x), bn, skip, relu)."""
+    if not conv1x1_fused_ok(conv, bn, x, skip):
+        return bn_act(conv(x), bn, skip=skip, relu=relu)
+    n, _, h, w = x.shape
+    y = torch.empty(n, conv.out_channels, h, w, dtype=torch.float32, device=x.device)
+    call('frh_conv1x1_bn_act', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), ptr(bn.weight), ptr(bn.bias),
+         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), n, conv.in_channels, conv.out_channels, h * w,
+         int(bool(relu)), stream_of(x))
+    return y
+
+
 def bn_act_maxpool(x, bn, pool):
     """pool(relu(bn(x))) for the ResNet stem (eval-mode BN, MaxPool2d(3, 2, 1)) in one HIP pass
     (frh_bn_act_maxpool) when nothing needs a gradient through it (the reference freezes the

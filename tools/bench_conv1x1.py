@@ -1,0 +1,152 @@
+"""Per-shape timing of frh_conv1x1_bn_act against the path it replaces.
+
+    python tools/bench_conv1x1.py [--iters 40] [--out profiles/conv1x1/bench_conv1x1.json]
+
+For every 1x1 / stride-1 convolution of the cfg2 trunk (ResNet-50, 2 images of 608 x 1024;
+cin -> cout @ hw, with its count per step and its epilogue form) it times
+  parent: F.conv2d (cudnn.benchmark warmed: MIOpen / Tensile) followed by ops.bn_act,
+  fused:  ops.conv1x1_bn_act's entry (frh_conv1x1_bn_act, the product's step choice),
+  steps:  both cin steps per barrier (16, 32), through the tools library (tools/build_tools.py),
+all under no_grad, `iters` calls back to back behind a torch.cuda._sleep between one event
+pair, 3 repetitions with the sides alternating (median reported), rotating over three sets of
+tensors so a call does not find its own output in the caches.
+
+Per shape it prints us for both paths, FLOPs, algorithmic bytes of the fused op (x, w, skip
+read once, y written once) and the share of the binding limit the fused kernel reaches,
+the limit being the larger of FLOPs / 157.3 TFLOP/s and bytes / 8 TB/s.  The weighted sums
+are the per-step totals of the 33 launches."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+sys.path.insert(0, HERE)
+
+N = 2
+# (cin, cout, hw, launches per step, skip, relu, where)
+SHAPES = [
+    (64, 64, 38912, 1, False, True, 'stage 1 block 0 conv1'),
+    (256, 64, 38912, 2, False, True, 'stage 1 conv1'),
+    (64, 256, 38912, 1, False, False, 'stage 1 projection'),
+    (64, 256, 38912, 3, True, True, 'stage 1 conv3'),
+    (256, 128, 38912, 1, False, True, 'stage 2 block 0 conv1'),
+    (512, 128, 9728, 3, False, True, 'stage 2 conv1'),
+    (128, 512, 9728, 4, True, True, 'stage 2 conv3'),
+    (512, 256, 9728, 1, False, True, 'stage 3 block 0 conv1'),
+    (1024, 256, 2432, 5, False, True, 'stage 3 conv1'),
+    (256, 1024, 2432, 6, True, True, 'stage 3 conv3'),
+    (1024, 512, 2432, 1, False, True, 'stage 4 block 0 conv1'),
+    (2048, 512, 608, 2, False, True, 'stage 4 conv1'),
+    (512, 2048, 608, 3, True, True, 'stage 4 conv3'),
+]
+PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
+SETS = 3
+
+
+def time_calls(fns, iters):
+    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(100000000)
+    e0.record()
+    for i in range(iters):
+        fns[i % len(fns)]()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=40)
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'conv1x1', 'bench_conv1x1.json'))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_conv1x1 needs a HIP device')
+    from frcnn_amd import _lib, ops
+    try:
+        import toolslib
+        tools = toolslib.load()
+    except (RuntimeError, OSError, AttributeError) as e:
+        print('tools library unavailable ({}): cin steps not timed'.format(e), file=sys.stderr)
+        tools = None
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    p = _lib.ptr
+    rows = []
+    with torch.no_grad():
+        for cin, cout, hw, count, skip, relu, where in SHAPES:
+            h, w = hw // 32, 32
+            assert h * w == hw, 'plane {} is not a multiple of 32'.format(hw)
+            conv = torch.nn.Conv2d(cin, cout, 1, bias=False).to(dev)
+            bn = torch.nn.BatchNorm2d(cout).to(dev).eval()
+            bn.running_var.uniform_(0.5, 2.0)
+            bn.running_mean.uniform_(-1, 1)
+            xs = [torch.randn(N, cin, h, w, device=dev) for _ in range(SETS)]
+            sk = [torch.randn(N, cout, h, w, device=dev) if skip else None for _ in range(SETS)]
+            ys = [torch.empty(N, cout, h, w, device=dev) for _ in range(SETS)]
+
+            def parent(i):
+                return lambda: ops.bn_act(F.conv2d(xs[i], conv.weight), bn, skip=sk[i], relu=relu)
+
+            def entry(i, tile=None):  # tile: the cin step, None = the product's choice
+                a = (p(xs[i]), p(conv.weight), p(sk[i]), p(ys[i]), p(bn.weight), p(bn.bias), p(bn.running_mean),
+                     p(bn.running_var), float(bn.eps), N, cin, cout, hw, int(relu), _lib.stream_of(xs[i]))
+                if tile is None:
+                    return lambda: _lib.call('frh_conv1x1_bn_act', *a)
+
+                def run():
+                    if tools.frh_conv1x1_bn_act_step(tile, *a) != 0:
+                        raise RuntimeError('frh_conv1x1_bn_act_step({}) failed'.format(tile))
+                return run
+            sides = {'parent': [parent(i) for i in range(SETS)], 'fused': [entry(i) for i in range(SETS)]}
+            if tools is not None:
+                for t in (16, 32):
+                    sides['step{}'.format(t)] = [entry(i, t) for i in range(SETS)]
+            for fns in sides.values():
+                for f in fns:
+                    f()
+                    f()
+            torch.cuda.synchronize()
+            ref, got = sides['parent'][0](), ys[0]
+            sides['fused'][0]()
+            maxdiff = float((ref - got).abs().max() / ref.abs().max())
+            t = {k: [] for k in sides}
+            for _ in range(3):
+                for k, fns in sides.items():
+                    t[k].append(time_calls(fns, args.iters))
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            flops = 2.0 * N * cin * cout * hw
+            nbytes = 4.0 * (N * hw * (cin + cout * (2 if skip else 1)) + cin * cout)
+            limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
+            row = {'where': where, 'cin': cin, 'cout': cout, 'hw': hw, 'launches_per_step': count, 'skip': skip,
+                   'relu': relu, 'excluded_in_ops': (cin, cout) in ops._CONV1X1_EXCLUDED, 'parent_us': round(med['parent'], 2), 'fused_us': round(med['fused'], 2),
+                   'steps_us': {k: round(v, 2) for k, v in med.items() if k.startswith('step')},
+                   'gflop': round(flops / 1e9, 3), 'algorithmic_MB': round(nbytes / 1e6, 2),
+                   'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
+                   'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / med['fused'], 3),
+                   'fused_TFLOPs': round(flops / med['fused'] / 1e6, 1), 'fused_TBps': round(nbytes / med['fused'] / 1e6, 2),
+                   'max_rel_diff_vs_parent': maxdiff}
+            rows.append(row)
+            print('{:24s} {:5d}->{:4d} @{:6d} x{}  parent {:8.2f} us  fused {:8.2f} us  {}  limit {:7.2f} us ({}, {:.0%})'
+                  .format(where, cin, cout, hw, count, med['parent'], med['fused'], row['steps_us'], limit_us,
+                          row['limit'], row['fused_share_of_limit']), flush=True)
+            del xs, sk, ys
+    res = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'batch': N, 'shapes': rows,
+           'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
+           'per_step_fused_us': round(sum(r['fused_us'] * r['launches_per_step'] for r in rows), 1)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k != 'shapes'}))
+
+
+if __name__ == '__main__':
+    main()

@@ -110,6 +110,12 @@ int32_t frh_sample_random_stamped(int32_t num_segs, const int64_t* labels_in, in
                                   uint64_t seed, int64_t* labels_out, int32_t* sel, int32_t* sel_counts,
                                   int32_t* status, void* workspace, size_t ws_bytes, int64_t* stamps, void* stream);
 
+/* frh_conv1x1_bn_act with the cin step per barrier (16 or 32, cin % step == 0) given instead
+ * of chosen (conv1x1_kernels.h). */
+int32_t frh_conv1x1_bn_act_step(int32_t step, const float* x, const float* w, const float* skip, float* y,
+                                const float* gamma, const float* beta, const float* mean, const float* var, float eps,
+                                int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

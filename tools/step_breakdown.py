@@ -23,6 +23,7 @@ CLASSES = [
     ('assignment', ('assign_',)),
     ('sampler compaction', ('chunk_',)),
     ('fused losses', ('cls_loss', 'smooth_l1', 'loss_finalize')),
+    ('fused 1x1 conv + frozen-BN/residual/ReLU', ('conv1x1_bn_act',)),
     ('frozen-BN/residual/ReLU bn_act', ('bn_act',)),
     ('FPN merge (+ lateral bias), RPN conv bias + ReLU', ('fpn_merge', 'bias_act')),
     ('other frcnn_amd kernels', ('frh::',)),
