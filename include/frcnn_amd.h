@@ -538,6 +538,35 @@ int32_t frh_conv1x1_bn_act(const float* x, const float* w, const float* skip, fl
                            const float* beta, const float* mean, const float* var, float eps, int64_t n,
                            int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream);
 
+/* The FPN output convs and the RPN head's shared conv (lib/necks.py, FPN.forward;
+ * lib/heads/rpn_head.py, RPNHead.forward): y = act(conv3x3(x, w) + bias), padding 1, stride 1,
+ * no dilation, no groups, as Winograd F(2x2, 3x3) on the f32 MFMA with the bias / ReLU
+ * epilogue on the accumulators (two launches: the weight transform into the workspace, which
+ * is redone on every call, then the convolution).
+ * x: f32 [n, h, wd, cin] with channel stride 1 and element strides sn / sy / sx (image, row,
+ * column; multiples of 4, so a strided view such as P5[:, :, ::2, ::2] runs without a copy);
+ * w: the channels-last Conv2d weight [cout][3][3][cin]; bias [cout] or NULL; y: contiguous
+ * NHWC [n, h, wd, cout]; workspace: frh_conv3x3_workspace(cin, cout) bytes.  cin % 8 == 0,
+ * cout % 64 == 0, every pointer 16-byte aligned, y not overlapping x or the workspace
+ * (anything else: FRH_EINVAL); any h, wd >= 1.  The sums run in a fixed order with no atomics:
+ * the same inputs give the same bits on every launch, and given the same pre-bias value the
+ * epilogue gives frh_bias_act_nhwc's bits.
+ * _levels: num_levels (1..8) inputs xs[i] [n, level_hw[2i], level_hw[2i + 1], cin] with
+ * strides level_strides[3i..] = (sn, sy, sx), weights[i], biases[i] (entries may be NULL) and
+ * outputs ys[i] in one weight-transform launch and one convolution launch.  Consecutive levels
+ * with the same weights pointer share one transform; the workspace holds
+ * frh_conv3x3_workspace(cin, cout) bytes per distinct weight.  Each level's bits are those of
+ * its own frh_conv3x3_bias_act call. */
+size_t frh_conv3x3_workspace(int32_t cin, int32_t cout);
+int32_t frh_conv3x3_bias_act(const float* x, const float* w, const float* bias, float* y, float* workspace,
+                             int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd, int64_t sn, int64_t sy,
+                             int64_t sx, int32_t relu, void* stream);
+int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, const void* const* weights,
+                                    const void* const* biases, void* const* ys, float* workspace,
+                                    size_t workspace_bytes, int64_t n, int32_t cin, int32_t cout,
+                                    const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
+                                    void* stream);
+
 /* FPN top-down merge into channels-last levels (lib/necks.py:72-84):
  * out[b, y, x, c] = (lat[b, c, y, x] + bias[c]) + up[b, iy, ix, c] with torch's nearest rule
  * (iy = min(floor(y * (float)up_h / height), up_h - 1); y / 2 when height == 2 * up_h);

@@ -152,7 +152,9 @@ class FPN(ChannelsLastConvs):
             lat = [conv(inputs[self.start_level + i]) for i, conv in enumerate(self.lateral_convs)]
             for i in range(self.used_ins - 1, 0, -1):
                 lat[i - 1] = lat[i - 1] + F.interpolate(lat[i], size=lat[i - 1].shape[2:], mode='nearest')
-        outs = [self.fpn_convs[i](lat[i]) for i in range(self.used_ins)]
+        # output convs: all levels in one fused Winograd launch where nothing needs a gradient,
+        # else the modules
+        outs = ops.conv3x3_bias_act_levels(list(self.fpn_convs)[:self.used_ins], lat)
         for i in range(self.used_ins, self.num_outs):
             if self.extra_use_convs:
                 src = inputs[self.end_level - 1] if (i == self.used_ins and self.extra_convs_on_inputs) else outs[-1]

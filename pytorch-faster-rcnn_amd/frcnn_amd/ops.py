@@ -1254,6 +1254,85 @@ def conv1x1_bn_act(conv, bn, x, skip=None, relu=True):
     return y
 
 
+# Level sizes (h, w) at which tools/bench_conv3x3.py measured a frh_conv3x3_bias_act call of
+# that level alone slower than the MIOpen NHWC conv followed by its bias (+ ReLU) pass (too few
+# workgroups for the chip; both times in DESIGN section 4): alone they keep that path, in a
+# multi-level launch beside a larger level they ride along.
+_CONV3X3_EXCLUDED = frozenset([(38, 64), (19, 32), (10, 16)])
+
+
+def conv3x3_fused_ok(conv, x, alone=True):
+    """Whether conv3x3_bias_act takes the fused HIP entry for these arguments (alone=False:
+    as one level of a multi-level launch, where the size exclusions do not apply)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.weight.dtype == torch.float32
+            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
+            and conv.weight.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    cout, cin = conv.out_channels, conv.in_channels
+    n, c, h, w = x.shape
+    sn, sc, sy, sx = x.stride()
+    if c != cin or cin % 8 or cout % 64 or n == 0 or h == 0 or w == 0 or (alone and (h, w) in _CONV3X3_EXCLUDED):
+        return False
+    if sc != 1 or sx < cin or sy < 0 or sn < 0 or (sn | sy | sx) % 4 \
+            or (h - 1) * sy + (w - 1) * sx + cin >= 1 << 30:
+        return False
+    if (x.data_ptr() | conv.weight.data_ptr() | (conv.bias.data_ptr() if conv.bias is not None else 0)) % 16:
+        return False
+    return not _needs_grad(x, conv.weight, conv.bias)
+
+
+def _conv3x3_ws(cin, cout, dev):
+    """The transformed-weight workspace of one call (every call rewrites it)."""
+    return torch.empty(16 * cin * cout, dtype=torch.float32, device=dev)
+
+
+def conv3x3_bias_act(conv, x, relu=False):
+    """act(conv(x)) for a 3x3 / stride-1 / padding-1 Conv2d on a channels-last (or channel-stride-1
+    strided) f32 HIP input in one fused launch pair (frh_conv3x3_bias_act: Winograd F(2x2, 3x3)
+    on the f32 MFMA, bias / ReLU on the accumulators) when nothing needs a gradient through it
+    (the graphed trunk, inference); otherwise conv_bias_relu / the module."""
+    if not conv3x3_fused_ok(conv, x):
+        return conv_bias_relu(conv, x) if relu else conv(x)
+    n, _, h, w = x.shape
+    sn, _, sy, sx = x.stride()
+    y = _nhwc_empty((n, conv.out_channels, h, w), x.device)
+    call('frh_conv3x3_bias_act', ptr(x), ptr(conv.weight), ptr(conv.bias), ptr(y),
+         ptr(_conv3x3_ws(conv.in_channels, conv.out_channels, x.device)), n, conv.in_channels, conv.out_channels, h, w,
+         sn, sy, sx, int(bool(relu)), stream_of(x))
+    return y
+
+
+def conv3x3_bias_act_levels(convs, xs, relu=False):
+    """conv3x3_bias_act on every level of a pyramid, convs one shared Conv2d (the RPN head) or one
+    per level (the FPN output convs): one weight-transform launch and one convolution launch
+    (frh_conv3x3_bias_act_levels) for the levels that can take the fused entry, provided one of
+    them would take it alone; conv3x3_bias_act for the others.  Same bits as the per-level calls."""
+    xs = list(xs)
+    convs = [convs] * len(xs) if isinstance(convs, nn.Module) else list(convs)
+    if len(convs) != len(xs):
+        raise AssertionError('conv3x3_bias_act_levels: one conv, or one per level')
+    fused = [i for i, (c, x) in enumerate(zip(convs, xs)) if conv3x3_fused_ok(c, x, alone=False)]
+    if fused:
+        c0, x0 = convs[fused[0]], xs[fused[0]]
+        fused = [i for i in fused if (convs[i].in_channels, convs[i].out_channels, xs[i].shape[0], xs[i].device)
+                 == (c0.in_channels, c0.out_channels, x0.shape[0], x0.device)][:8]
+    if len(fused) < 2 or not any(conv3x3_fused_ok(convs[i], xs[i]) for i in fused):
+        return [conv3x3_bias_act(c, x, relu) for c, x in zip(convs, xs)]
+    outs = [None if i in fused else conv3x3_bias_act(c, x, relu) for i, (c, x) in enumerate(zip(convs, xs))]
+    fx, fc = [xs[i] for i in fused], [convs[i] for i in fused]
+    n, dev, cin, cout = fx[0].shape[0], fx[0].device, fc[0].in_channels, fc[0].out_channels
+    ys = [_nhwc_empty((n, cout, x.shape[2], x.shape[3]), dev) for x in fx]
+    distinct = 1 + sum(1 for a, b in zip(fc, fc[1:]) if a.weight.data_ptr() != b.weight.data_ptr())
+    ws = _conv3x3_ws(cin, cout * distinct, dev)
+    call('frh_conv3x3_bias_act_levels', len(fx), ptr_array(fx), ptr_array([c.weight for c in fc]),
+         _ptrs_or_null([c.bias for c in fc]), ptr_array(ys), ptr(ws), ws.numel() * 4, n, cin, cout,
+         i32_array([v for x in fx for v in x.shape[2:]]),
+         i64_array([v for x in fx for v in (x.stride(0), x.stride(2), x.stride(3))]), int(bool(relu)), stream_of(fx[0]))
+    for i, y in zip(fused, ys):
+        outs[i] = y
+    return outs
+
 def bn_act_maxpool(x, bn, pool):
     """pool(relu(bn(x))) for the ResNet stem (eval-mode BN, MaxPool2d(3, 2, 1)) in one HIP pass
     (frh_bn_act_maxpool) when nothing needs a gradient through it (the reference freezes the
