@@ -687,6 +687,58 @@ int32_t frh_det_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int
                          const int32_t* status, float* out, void* workspace, size_t ws_bytes,
                          void* stream);
 
+/* ---------------------------------------------------------------- f1b: GFL head losses
+ * The three losses of the Generalized Focal Loss head (FCOSHead.calc_loss with QualityFocalLoss,
+ * DistributionFocalLoss and GIoULoss: lib/heads/fcos_head.py:419-515 with lib/losses.py:13-30,
+ * :221-282 and utils.elem_iou, lib/utils.py:174-182) of one batch in ONE launch, straight from
+ * the head outputs: class logit (k, i) at cls[k*cls_sk + i*cls_si] (k < c), regression logit of
+ * channel ch = bin*4 + side (fcos_head.py:231, :464) at reg[ch*reg_sc + i*reg_si], label [m]
+ * int64 (-1 ignored, 0 negative, > 0 the class), ltrb [m, 4] f32 pixels; positions ordered
+ * images outer, levels inner.  For a positive j (label > 0, counted on the device):
+ * w_j = max_k sigmoid(cls(k, j)); y_s = (ltrb_s - reg_mean) / reg_std;
+ *   DFL (losses.py:265-282) per side: left = trunc(clamp(y, 0, (bins-1)*stride) / stride),
+ *     -(((left+1)*stride - y) * logsm[left] + (y - left*stride) * logsm[left+1]), / stride with
+ *     norm_prob; summed, * dfl_weight / dfl_avg_factor.  The weight the reference passes in is
+ *     unused there and here.
+ *     DIVERGENCE: at left == bins-1 (y >= (bins-1)*stride) the reference indexes bin `bins` and
+ *     raises IndexError; here that right-hand term is dropped and bin `bins` is never read.
+ *   box (fcos_head.py:474-483): len_s = sum_b softmax(z_s)[b] * b*stride, boxes
+ *     (-len_l, -len_t, len_r, len_b) against (-y_l, -y_t, y_r, y_b); giou_loss * w_j summed,
+ *     * bbox_weight / num_pos.  q_j = their plain IoU (no +1).
+ * QFL (losses.py:221-247) over every position with label >= 0 and class k: t = (label == k+1) ?
+ * q : 0, |t - sigmoid(x)|^beta * bce_with_logits(x, t), summed, * cls_weight / num_pos.
+ * out[4] = {cls_loss, dfl_loss, bbox_loss, (float)num_pos}; with no positive the sums are
+ * divided by max(num_pos, 1) (the reference raises).  status / workspace as frh_cls_loss_fwd
+ * (NaN losses while the status word is set); partial sums are finalised in a fixed order, no
+ * float atomics: two calls on one input are bit-identical.  bins*4 > 64: FRH_EUNSUPPORTED.
+ * Backward writes d(g[0]*cls_loss + g[1]*dfl_loss + g[2]*bbox_loss) / d logits: g [3] and
+ * fwd_out (the forward's out) are device memory (no host sync); every element of grad_cls
+ * (k, i) at grad_cls[k*gc_sk + i*gc_si] and grad_reg (ch, i) at grad_reg[ch*gr_sc + i*gr_si]
+ * is written exactly once (0 at ignored positions / at non-positive positions); q and w are
+ * constants, as the reference's detach()s make them. */
+int32_t frh_gfl_loss_fwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cls_si, const float* reg,
+                         int32_t bins, int64_t reg_sc, int64_t reg_si, const int64_t* label,
+                         const float* ltrb, int64_t m, float reg_mean, float reg_std, double stride,
+                         int32_t norm_prob, float beta, float cls_weight, float dfl_weight,
+                         float bbox_weight, float dfl_avg_factor, const int32_t* status, float* out,
+                         void* workspace, size_t ws_bytes, void* stream);
+int32_t frh_gfl_loss_bwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cls_si, const float* reg,
+                         int32_t bins, int64_t reg_sc, int64_t reg_si, const int64_t* label,
+                         const float* ltrb, int64_t m, float reg_mean, float reg_std, double stride,
+                         int32_t norm_prob, float beta, float cls_weight, float dfl_weight,
+                         float bbox_weight, float dfl_avg_factor, const float* g, const float* fwd_out,
+                         float* grad_cls, int64_t gc_sk, int64_t gc_si, float* grad_reg, int64_t gr_sc,
+                         int64_t gr_si, void* stream);
+/* The DFL ("integral") box decode of one level for a batch (FCOSHead.predict_single_image,
+ * fcos_head.py:579-600 with ltrb2bbox :63-75 and utils.clamp_bbox, lib/utils.py:109-120):
+ * reg [batch, 4*bins, h, w] f32 with element strides (sb, sc, sy, sx) -- any layout, channels-
+ * last included; per side the softmax expectation sum_b p_b * b*stride, * reg_std + reg_mean;
+ * the box around the cell centre (x*cell + cell/2, y*cell + cell/2), clamped to
+ * [0, img_w-1] x [0, img_h-1]; boxes [batch, 4, h*w] contiguous.  bins*4 > 64: FRH_EUNSUPPORTED. */
+int32_t frh_dfl_decode(const float* reg, int32_t batch, int32_t bins, int32_t h, int32_t w, int64_t sb,
+                       int64_t sc, int64_t sy, int64_t sx, double stride, float reg_std, float reg_mean,
+                       float cell, float img_h, float img_w, float* boxes, void* stream);
+
 /* ---------------------------------------------------------------- f4: image pipeline
  * The train/test pipelines of configs/faster_rcnn_r50_fpn.py:120-139 (mmdet v1: Resize
  * keep_ratio -> RandomFlip -> Normalize -> Pad(size_divisor) -> DefaultFormatBundle ->

@@ -32,7 +32,7 @@
 // Numerics follow torch's formulas (binary_cross_entropy_with_logits via
 // log_sigmoid, pow backward, log_softmax backward); sums differ from torch's
 // reduction order in the last bits, gradients agree to a few ulp.
-#include "common.h"
+#include "loss_common.h"
 
 #include <math.h>
 
@@ -40,10 +40,6 @@
 
 namespace frh {
 namespace {
-
-constexpr int kLossThreads = 256;
-constexpr int kMaxPartials = 256;   // forward grid cap = partial slots
-constexpr int kCounterBytes = 256;  // arrival counter block at the workspace start
 
 enum ClsKind { kFocal = 0, kSigmoidBce = 1, kSoftmaxCe = 2 };
 
@@ -69,15 +65,6 @@ __device__ __forceinline__ int64_t label_at(const ClsArgs& a, int64_t i) {
 // frh_bbox_target past their device count): they contribute nothing, forward or backward
 // (the reference's sampled targets never carry such labels)
 __device__ __forceinline__ bool ignored(const ClsArgs& a, int64_t i) { return !a.tfloat && label_at(a, i) < 0; }
-
-// torch: binary_cross_entropy_with_logits = (1 - t) * x - log_sigmoid(x),
-// log_sigmoid(x) = min(x, 0) - log1p(exp(-|x|)).
-__device__ __forceinline__ float bce_logits(float x, float t) {
-  float ls = fminf(x, 0.0f) - log1pf(expf(-fabsf(x)));
-  return (1.0f - t) * x - ls;
-}
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // sigmoid_focal_loss element (losses.py:48-61) and its derivative.
 __device__ __forceinline__ float focal_elem(float x, float t, float alpha, float gamma, float* dx) {
@@ -115,31 +102,12 @@ __device__ __forceinline__ float elem_target(const ClsArgs& a, int64_t i, int64_
   return label_at(a, i) == k + 1 ? 1.0f : 0.0f;
 }
 
-__device__ __forceinline__ float block_sum_f(float v, float* scratch) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  const int w = threadIdx.x >> 6;
-  if (lane_id() == 0) scratch[w] = v;
-  __syncthreads();
-  float t = 0.0f;
-  if (threadIdx.x == 0)
-    for (int j = 0; j < kLossThreads / kWave; ++j) t += scratch[j];
-  return t;
-}
-
 struct FanIn {
   uint32_t* counter;      // zero between calls
   float* partial;         // [gridDim.x]
   float* out;
   const int32_t* status;  // nullable: the caller's device status word; nonzero -> NaN loss
 };
-
-// A nonzero device status word (an in-launch wait of an earlier one-launch kernel ran out,
-// include/frcnn_amd.h FRH_DEVERR_*) makes the loss NaN: the outputs it was computed from are
-// undefined, and the step's own loss read carries the failure without an extra host sync.
-__device__ __forceinline__ bool status_set(const int32_t* status) {
-  return status && __hip_atomic_load(const_cast<int32_t*>(status), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-}
 
 // Thread 0 holds the workgroup's partial sum.  The last workgroup to arrive sums
 // all partials in a fixed order (double accumulation: one slot per thread, then
@@ -532,7 +500,7 @@ using namespace frh;
 
 extern "C" {
 
-size_t frh_loss_workspace(void) { return kCounterBytes + 2 * kMaxPartials * sizeof(float); }
+size_t frh_loss_workspace(void) { return kCounterBytes + kLossPartialArrays * kMaxPartials * sizeof(float); }
 
 static FanIn fan_in(void* workspace, float* out, const int32_t* status) {
   char* w = static_cast<char*>(workspace);

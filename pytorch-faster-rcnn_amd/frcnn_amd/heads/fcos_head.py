@@ -2,9 +2,12 @@
 
 ATSS targets (fcos_head.py:283-368) for every image of the batch
 come from one `ops.atss_assign` call (frh_atss_assign: fill, per-(gt, level)
-top-k, per-image resolve); the plain FCOS scale-range targets
-(fcos_head.py:371-420), the losses (:418-534, focal / GIoU / centerness, QFL,
-DFL) and inference (:566-627) are PyTorch-ROCm tensor code around them.
+top-k, per-image resolve).  The GFL head (QFL + DFL + GIoU, :419-515) computes its
+three losses in one `ops.gfl_losses` launch (frh_gfl_loss_fwd / _bwd) and decodes its
+boxes with `ops.dfl_decode` (frh_dfl_decode, :579-600).  The plain FCOS scale-range
+targets (fcos_head.py:371-420), the other loss combinations (focal / GIoU /
+centerness, QFL alone, DFL alone) and the rest of inference (:566-627) are
+PyTorch-ROCm tensor code around them.
 The LTRB helpers keep the reference's names and semantics.
 """
 import logging
@@ -14,7 +17,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import ops, utils
+from .. import losses, ops, utils
 from ..anchor import AnchorCreator
 from ..utils import ChannelsLastConvs
 
@@ -262,6 +265,19 @@ class FCOSHead(ChannelsLastConvs):
     def calc_loss_flat(self, cls_outs, reg_outs, ctr_outs, cls_tars, reg_tars, ctr_tars):
         """fcos_head.py:418-534 on batch-flattened tensors: cls_outs [C, M], reg_outs [4|4*bins, M],
         ctr_outs [1, M], cls_tars [M], reg_tars [M, 4], ctr_tars [M] (images outer, levels inner)."""
+        if self.use_qfl and self.use_dfl and isinstance(self.loss_bbox, losses.GIoULoss):
+            # GFL: the three losses straight from the un-indexed flat tensors -- one HIP launch
+            # (csrc/gfl.hip, no host read of the positive count), or its torch restatement
+            # for CPU tensors and more than 16 bins
+            d = self.loss_dfl
+            fused = cls_outs.is_cuda and d.cls_channels * 4 <= 64
+            fn = ops.gfl_losses if fused else losses.gfl_head_losses_torch
+            cls_loss, dfl_loss, bbox_loss, _ = fn(
+                cls_outs, reg_outs, cls_tars, reg_tars, d.cls_channels, d.stride, reg_mean=self.reg_mean,
+                reg_std=self.reg_std, norm_prob=d.norm_prob, beta=self.loss_cls.beta,
+                cls_weight=self.loss_cls.loss_weight, dfl_weight=d.loss_weight,
+                bbox_weight=self.loss_bbox.loss_weight, dfl_avg_factor=4.0)
+            return OrderedDict([('cls_loss', cls_loss), ('dfl_loss', dfl_loss), ('bbox_loss', bbox_loss)])
         chosen = cls_tars >= 0
         pos = cls_tars > 0
         num_pos = int(pos.sum())
@@ -344,7 +360,11 @@ class FCOSHead(ChannelsLastConvs):
         img_size = img_meta['img_shape'][:2]
         bboxes, scores, ctrs = [], [], []
         for i in range(len(cls_outs)):
-            if self.use_dfl:
+            if self.use_dfl and reg_outs[i].is_cuda and self.loss_dfl.cls_channels * 4 <= 64:
+                # softmax expectation, box and clamp of the level in one launch (csrc/gfl.hip)
+                bbox = ops.dfl_decode(reg_outs[i].unsqueeze(0), self.loss_dfl.cls_channels, self.loss_dfl.stride,
+                                      self.reg_std, self.reg_mean, self.strides[i], img_size)[0]
+            elif self.use_dfl:
                 r = reg_outs[i]
                 gs = r.shape[-2:]
                 r = r.reshape(self.loss_dfl.cls_channels, -1).t().softmax(-1)

@@ -274,3 +274,56 @@ class DistributionFocalLoss(nn.Module):
         if self.norm_prob:
             loss = loss / self.stride
         return -loss.sum() * self.loss_weight / avg_factor
+
+
+def gfl_head_losses_torch(cls_outs, reg_outs, labels, ltrb, bins, stride, reg_mean=0.0, reg_std=1.0,
+                          norm_prob=False, beta=2.0, cls_weight=1.0, dfl_weight=1.0, bbox_weight=1.0,
+                          dfl_avg_factor=4.0):
+    """The GFL head's three losses (reference FCOSHead.calc_loss with QualityFocalLoss,
+    DistributionFocalLoss and GIoULoss, fcos_head.py:419-515) restated in torch ops, expression
+    for expression: the numerics reference of ops.gfl_losses (csrc/gfl.hip) and what FCOSHead
+    runs off the fused path.  CPU (f32 / f64) or HIP tensors; no ops call.
+
+    cls_outs [C, M] and reg_outs [4*bins, M] logits (regression channel = bin*4 + side), labels
+    [M] int64 (-1 ignored, 0 negative, > 0 the class), ltrb [M, 4] pixels; positions ordered
+    images outer, levels inner.  Returns (cls_loss, dfl_loss, bbox_loss, num_pos [int64 0-d]).
+
+    Two points where the reference raises and this (like the kernel) does not: with no positive
+    the sums are divided by max(num_pos, 1); and a target in the top bin (left == bins-1, the
+    reference indexes bin `bins`) keeps the left-hand DFL term only."""
+    chosen, pos = labels >= 0, labels > 0
+    num_pos = pos.sum()
+    div = num_pos.clamp(min=1).to(cls_outs.dtype)
+    w, _ = cls_outs.detach()[:, pos].sigmoid().max(0)
+    y4 = (ltrb[pos, :].t() - reg_mean) / reg_std                       # [4, m]
+    y = y4.contiguous().view(-1)                                       # [4m], side-major
+    # length2class (fcos_head.py:10-29): f32 whatever the input's dtype
+    left = (y.float().clamp(0, (bins - 1) * stride) / stride).long()
+    right = left + 1
+    x = reg_outs[:, pos].reshape(bins, -1).t()                         # [4*bins, m] -> [bins, 4m] -> [4m, bins]
+    ar = torch.arange(x.shape[0], device=x.device)
+    log_sigma = log_softmax_with_logits(x)
+    y_left, y_right = left * stride, right * stride
+    right_term = (y - y_left) * log_sigma[ar, right.clamp(max=bins - 1)]
+    loss = (y_right - y) * log_sigma[ar, left] + torch.where(right < bins, right_term, torch.zeros_like(right_term))
+    if norm_prob:
+        loss = loss / stride
+    dfl_loss = -loss.sum() * dfl_weight / dfl_avg_factor
+    # class2length (fcos_head.py:32-42) and simple_ltrb2bbox around (0, 0)
+    rand_var = x.new_tensor([i * stride for i in range(bins)])
+    out4 = (x.softmax(-1) * rand_var).sum(-1).view(4, -1)
+    a = torch.stack([0.0 - out4[0], 0.0 - out4[1], 0.0 + out4[2], 0.0 + out4[3]])
+    b = torch.stack([0.0 - y4[0], 0.0 - y4[1], 0.0 + y4[2], 0.0 + y4[3]])
+    a_d = a.detach()
+    tl, br = torch.max(a_d[:2], b[:2]), torch.min(a_d[2:], b[2:])      # utils.elem_iou (lib/utils.py:174-182)
+    area_i = torch.prod(br - tl, dim=0) * (tl < br).all(0).float()
+    quality = area_i / (torch.prod(a_d[2:] - a_d[:2], dim=0) + torch.prod(b[2:] - b[:2], dim=0) - area_i)
+    bbox_loss = (giou_loss(a, b) * w).sum() * bbox_weight / div
+    q_all = quality.new_zeros(labels.numel())
+    q_all[pos] = quality
+    pred = cls_outs[:, chosen].t()
+    n, n_cls = pred.shape
+    tar = pred.new_zeros((n, n_cls + 1))
+    tar[torch.arange(n, device=pred.device), labels[chosen]] = q_all[chosen]
+    cls_loss = generalized_focal_loss(pred, tar[:, 1:], beta=beta).sum() * cls_weight / div
+    return cls_loss, dfl_loss, bbox_loss, num_pos

@@ -1568,3 +1568,71 @@ def det_losses(x, target, kind, alpha, gamma, cls_weight, l1_args, beta, reg_wei
         avg_factor = float(avg_factor)
     return _DetLoss.apply(_f32(x), target.contiguous(), int(kind), alpha, gamma, cls_weight, rx, ry, rlabel, xs, ys,
                           rn, rm, n_sel, beta, reg_weight, avg_factor)
+
+
+# ---------------------------------------------------------------- f1b: GFL head losses, DFL decode
+class _GflLoss(torch.autograd.Function):
+    """QFL / DFL / GIoU losses of the GFL head in one launch (frh_gfl_loss_fwd), one launch
+    backward (frh_gfl_loss_bwd); the positive count and the upstream gradients stay on the device."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, labels, ltrb, cfg):
+        out = torch.empty(4, dtype=torch.float32, device=cls.device)
+        ws = _loss_workspace(cls)
+        call('frh_gfl_loss_fwd', *_gfl_args(cls, reg, labels, ltrb, cfg), ptr(status_word(cls.device)), ptr(out),
+             ptr(ws), ws.numel(), stream_of(cls))
+        ctx.save_for_backward(cls, reg, labels, ltrb, out)
+        ctx.cfg = cfg
+        num_pos = out[3].long()
+        ctx.mark_non_differentiable(num_pos)
+        return out[0], out[1], out[2], num_pos
+
+    @staticmethod
+    def backward(ctx, gc, gd, gb, _):
+        cls, reg, labels, ltrb, out = ctx.saved_tensors
+        g = _f32(torch.stack([gc, gd, gb])).contiguous()
+        gcls, greg = torch.empty_like(cls), torch.empty_like(reg)
+        call('frh_gfl_loss_bwd', *_gfl_args(cls, reg, labels, ltrb, ctx.cfg), ptr(g), ptr(out), ptr(gcls),
+             gcls.stride(0), gcls.stride(1), ptr(greg), greg.stride(0), greg.stride(1), stream_of(cls))
+        return gcls, greg, None, None, None
+
+
+def _gfl_args(cls, reg, labels, ltrb, cfg):
+    bins, stride, reg_mean, reg_std, norm_prob, beta, wc, wd, wb, avg = cfg
+    return (ptr(cls), cls.shape[0], cls.stride(0), cls.stride(1), ptr(reg), bins, reg.stride(0), reg.stride(1),
+            ptr(labels), ptr(ltrb), cls.shape[1], reg_mean, reg_std, stride, norm_prob, beta, wc, wd, wb, avg)
+
+
+def gfl_losses(cls_outs, reg_outs, labels, ltrb, bins, stride, reg_mean=0.0, reg_std=1.0, norm_prob=False, beta=2.0,
+               cls_weight=1.0, dfl_weight=1.0, bbox_weight=1.0, dfl_avg_factor=4.0):
+    """(cls_loss, dfl_loss, bbox_loss, num_pos) of the GFL head (csrc/gfl.hip; the arguments and
+    semantics of losses.gfl_head_losses_torch): cls_outs [C, M] and reg_outs [4*bins, M] f32 logits
+    in any strides, labels [M] int64, ltrb [M, 4].  The losses are 0-d tensors, num_pos a 0-d
+    int64 device tensor; nothing is read back to the host.  4*bins > 64 raises."""
+    _need_cuda(cls_outs, reg_outs, labels, ltrb)
+    if cls_outs.dim() != 2 or reg_outs.dim() != 2 or reg_outs.shape[0] != 4 * bins:
+        raise AssertionError('gfl_losses: cls_outs [C, M] and reg_outs [4*bins, M] expected')
+    m = cls_outs.shape[1]
+    if reg_outs.shape[1] != m or labels.shape != (m,) or ltrb.shape != (m, 4):
+        raise AssertionError('gfl_losses: labels [M] and ltrb [M, 4] must match the logits')
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    cfg = (int(bins), float(stride), float(reg_mean), float(reg_std), int(bool(norm_prob)), float(beta),
+           float(cls_weight), float(dfl_weight), float(bbox_weight), float(dfl_avg_factor))
+    return _GflLoss.apply(_f32(cls_outs), _f32(reg_outs), labels.contiguous(), _f32(ltrb).contiguous(), cfg)
+
+
+def dfl_decode(reg, bins, stride, reg_std, reg_mean, cell, img_size):
+    """Boxes [B, 4, H*W] of one level's DFL regression logits reg [B, 4*bins, H, W] (any strides):
+    softmax expectation per side, * reg_std + reg_mean, the box around the cell centre (cell =
+    the level's stride), clamped to img_size (h, w) (frh_dfl_decode; fcos_head.py:579-600)."""
+    _need_cuda(reg)
+    if reg.dim() != 4 or reg.shape[1] != 4 * bins:
+        raise AssertionError('dfl_decode: reg [B, 4*bins, H, W] expected')
+    reg = _f32(reg)
+    B, _, h, w = reg.shape
+    out = torch.empty(B, 4, h * w, dtype=torch.float32, device=reg.device)
+    call('frh_dfl_decode', ptr(reg), B, int(bins), h, w, reg.stride(0), reg.stride(1), reg.stride(2), reg.stride(3),
+         float(stride), float(reg_std), float(reg_mean), float(cell), float(img_size[0]), float(img_size[1]), ptr(out),
+         stream_of(reg))
+    return out
