@@ -18,11 +18,15 @@
 // x 64 output channels.  cin is walked in chunks of 8: 64 MFMAs per wave per chunk.  Per chunk
 //   - every thread loads the 4 x 4 pixels x float2 of its tile's patch (four threads per tile
 //     share the chunk's 8 channels), applies B^T d B and writes 16 float2 of V;
-//   - every thread copies 8 float4 of the U chunk, which the weights kernel wrote in the LDS
-//     image's own order.
-// Both go global -> registers -> LDS, two LDS stages, one barrier per chunk: the loads of chunk
-// t + 2 are in flight while chunk t runs its MFMAs, and chunk t + 1 is transformed and written
-// between them.  LDS images: V [16][64 tiles][8 k] and U [16][64 cout][8 k]; lane half h owns
+//   - every wave moves 8 KB of the U chunk, which the weights kernel wrote in the LDS image's
+//     own order, straight into LDS with 8 LDS-DMA instructions (global_load_lds_dwordx4).
+// Two LDS stages of each, one barrier per chunk.  While chunk t runs its MFMAs, U of chunk
+// t + 1 is in flight into the other U stage, the patch of chunk t + 2 is in flight into one of
+// two register sets, and the patch of chunk t + 1 (the other set, landed one step ago) is
+// transformed and written; all loads of a step are issued in its first 9 MFMAs and waited for
+// once, before its closing barrier.  The prologue is step -1 and past the last chunk the
+// prefetches repeat it, so every chunk count runs the same loop body and nothing is peeled.
+// LDS images: V [16][64 tiles][8 k] and U [16][64 cout][8 k]; lane half h owns
 // k = 4 h .. 4 h + 3 of the chunk (a fixed permutation of the k order), one ds_read_b128 per
 // operand and position.  A row's two 16-byte halves swap places when bit 3 of the row index is
 // set: each 16-lane group of a ds_read_b128 then reads 16 distinct 4-bank groups.
@@ -47,7 +51,10 @@ constexpr int kWgCout = 64;     // output channels per workgroup
 constexpr int kWgXcds = 8;
 constexpr int kWgMaxLevels = 8;
 constexpr int kWgSlab = 64 * kWgBK;             // floats of one position of V (or U) per chunk
-constexpr int kWgStage = 2 * 16 * kWgSlab;      // floats of one LDS stage: V then U
+constexpr int kWgImage = 16 * kWgSlab;          // floats of one LDS stage of V (or U)
+
+typedef uint32_t wg_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void* wg_lds_ptr;
 
 struct Conv3x3Level {
   const float* x;
@@ -128,8 +135,28 @@ __global__ void __launch_bounds__(256) conv3x3_bias_act_weights_kernel(const Con
   }
 }
 
+// A raw buffer descriptor over the memory from p on (p wave-uniform; both halves are read from
+// the first lane so that the compiler keeps it in SGPRs): loads through it take a 32-bit lane
+// offset and a scalar offset, no per-lane 64-bit address.  No range: every offset the kernel
+// forms is inside the tensor.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_buffer(const void* p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, -1, 0x00020000);
+}
+
+// p (wave-uniform) as an integer the compiler keeps in SGPRs
+__device__ __forceinline__ uint64_t wg_uniform64(const void* p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const Conv3x3Args a) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * kWgStage];  // 128 KB: two stages of V, U
+  // 128 KB, one array: U stages 0, 1 (the LDS-DMA's targets), then V stages 0, 1
+  __shared__ __attribute__((aligned(16))) float lds[4 * kWgImage];
 
   // XCD x takes logical workgroups [x * chunk, (x + 1) * chunk)
   const int wg = (int)(blockIdx.x % kWgXcds) * a.chunk + (int)(blockIdx.x / kWgXcds);
@@ -148,7 +175,7 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   const int cb = rest / a.n;
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int h = lane >> 5, j = lane & 31;
 
@@ -158,8 +185,9 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   const int T = tid >> 2, c2 = tid & 3;
   const int iy0 = (by * kWgSide + (T >> 3)) * 2 - 1;
   const int ix0 = (bx * kWgSide + (T & 7)) * 2 - 1;
-  // wave-uniform bases; the lane's part is a 32-bit byte offset (no address arithmetic per load)
-  const char* xb = reinterpret_cast<const char*>(L.x + (int64_t)img * L.sn);
+  // the image as a buffer; the lane's part is a 32-bit byte offset, the chunk's a scalar one
+  // (an image spans less than 2^32 bytes)
+  const __amdgpu_buffer_rsrc_t xb = wg_buffer(L.x + (int64_t)img * L.sn);
   uint32_t xoff[4][4];
   bool xok[4][4];
 #pragma unroll
@@ -172,36 +200,66 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
       xoff[r][c] = (uint32_t)(cy * L.sy + cx * L.sx + c2 * 2) * 4u;  // bytes
     }
   const int v_off = wg_slab_off(T, c2 >> 1) + (c2 & 1) * 2;
-  // U: float4 q * 256 + tid of the chunk's [16][64][8] image, q = 0 .. 7
-  const char* ub = reinterpret_cast<const char*>(L.u + (int64_t)cb * kWgCout * kWgBK);
-  const uint32_t u_src = (uint32_t)((tid >> 7) * a.cout * kWgBK + (tid & 127) * 4) * 4u;
-  const int64_t u_pos = (int64_t)2 * a.cout * kWgBK * 4;     // two positions on, bytes
-  const int64_t u_chunk = (int64_t)16 * a.cout * kWgBK * 4;  // one chunk on
-  const int u_off = 16 * kWgSlab + (tid >> 7) * kWgSlab + (tid & 127) * 4;
+  // U: the chunk's [16][64][8] image is 32 runs of 1 KB, in global memory (two per position,
+  // positions cout * 32 bytes apart) as in LDS (contiguous); one LDS-DMA instruction moves a
+  // run, lane l its 16 bytes at 16 l.  Wave w moves positions 4 w .. 4 w + 3.
+  const int64_t u_pos = (int64_t)a.cout * kWgBK * 4;  // one position on, bytes
+  const int64_t u_chunk = 16 * u_pos;                 // one chunk on
+  const char* ub = reinterpret_cast<const char*>(L.u + (int64_t)cb * kWgCout * kWgBK) + wave * 4 * u_pos;
+  const uint32_t u_lane = (uint32_t)lane * 16u;
+  const uint32_t u_dst = (uint32_t)(uintptr_t)(wg_lds_ptr)lds + (uint32_t)wave * 4 * kWgSlab * 4;  // LDS bytes
   // MFMA operands: A = V rows (tiles wm * 32 + j), B = U rows (channels wn * 32 + j), k half h
-  const int a_off = wg_slab_off(wm * 32 + j, h);
-  const int b_off = 16 * kWgSlab + wg_slab_off(wn * 32 + j, h);
+  const int a_off = 2 * kWgImage + wg_slab_off(wm * 32 + j, h);
+  const int b_off = wg_slab_off(wn * 32 + j, h);
 
-  // staging registers (named: an indexed array of them ends up in LDS)
-  wg_f32x2 x00, x01, x02, x03, x10, x11, x12, x13, x20, x21, x22, x23, x30, x31, x32, x33;
-  float4 u0, u1, u2, u3, u4, u5, u6, u7;
-#define FRH_WG_LX(r, c) x##r##c = *reinterpret_cast<const wg_f32x2*>(xs_ + xoff[r][c])
-#define FRH_WG_LU(q) *reinterpret_cast<const float4*>(up_ + (q) * u_pos + u_src)
-#define FRH_WG_LOAD(t)                                                                   \
-  do {                                                                                   \
-    const char* xs_ = xb + (t) * (kWgBK * 4);                                               \
-    FRH_WG_LX(0, 0), FRH_WG_LX(0, 1), FRH_WG_LX(0, 2), FRH_WG_LX(0, 3);                  \
-    FRH_WG_LX(1, 0), FRH_WG_LX(1, 1), FRH_WG_LX(1, 2), FRH_WG_LX(1, 3);                  \
-    FRH_WG_LX(2, 0), FRH_WG_LX(2, 1), FRH_WG_LX(2, 2), FRH_WG_LX(2, 3);                  \
-    FRH_WG_LX(3, 0), FRH_WG_LX(3, 1), FRH_WG_LX(3, 2), FRH_WG_LX(3, 3);                  \
-    const char* up_ = ub + (t) * u_chunk;                                                \
-    u0 = FRH_WG_LU(0), u1 = FRH_WG_LU(1), u2 = FRH_WG_LU(2), u3 = FRH_WG_LU(3);          \
-    u4 = FRH_WG_LU(4), u5 = FRH_WG_LU(5), u6 = FRH_WG_LU(6), u7 = FRH_WG_LU(7);          \
+  // two sets of patch registers (named: an indexed array of them ends up in LDS): chunk c
+  // lives in set c & 1, loaded two steps before the step that multiplies it
+  wg_f32x2 x000, x001, x002, x003, x010, x011, x012, x013, x020, x021, x022, x023, x030, x031, x032, x033;
+  wg_f32x2 x100, x101, x102, x103, x110, x111, x112, x113, x120, x121, x122, x123, x130, x131, x132, x133;
+  const wg_f32x2 z2 = {0.0f, 0.0f};
+#define FRH_WG_LX(S, r, c) \
+  x##S##r##c = __builtin_bit_cast(wg_f32x2, __builtin_amdgcn_raw_buffer_load_b64(xb, (int)xoff[r][c], xs_, 0))
+#define FRH_WG_LOADX(S, t)                                                                       \
+  do {                                                                                           \
+    const int xs_ = (t) * (kWgBK * 4);                                                           \
+    FRH_WG_LX(S, 0, 0), FRH_WG_LX(S, 0, 1), FRH_WG_LX(S, 0, 2), FRH_WG_LX(S, 0, 3);              \
+    FRH_WG_LX(S, 1, 0), FRH_WG_LX(S, 1, 1), FRH_WG_LX(S, 1, 2), FRH_WG_LX(S, 1, 3);              \
+    FRH_WG_LX(S, 2, 0), FRH_WG_LX(S, 2, 1), FRH_WG_LX(S, 2, 2), FRH_WG_LX(S, 2, 3);              \
+    FRH_WG_LX(S, 3, 0), FRH_WG_LX(S, 3, 1), FRH_WG_LX(S, 3, 2), FRH_WG_LX(S, 3, 3);              \
   } while (0)
 
-  // the U copy and B^T d B of the staged patch into stage ST: columns first (e = B^T d), then
-  // rows, each V row written as soon as it is complete
-#define FRH_WG_Z(r, c) (xok[r][c] ? x##r##c : z2)
+  // Chunk t of U into U stage ST by LDS-DMA: 8 instructions per wave, no registers.  In
+  // assembly, because the compiler makes every LDS read after a DMA it knows of wait for that
+  // DMA.  It does not count these, so FRH_WG_SYNC waits for them; the only orderings needed are
+  // held by operands: the token chains each DMA between the barriers before and after it, and
+  // `after` (a value made from the last patch register of the step) keeps it behind the
+  // compiler's counted waits for the patch loads, which it would otherwise tighten.  M0 is the
+  // LDS address of a run pair; it is the compiler's register, so it is put back.
+#define FRH_WG_DMA(ST, t, after)                                                                 \
+  do {                                                                                           \
+    const uint64_t g_ = wg_uniform64(ub + (int64_t)(t) * u_chunk);                               \
+    const uint32_t l_ = u_dst + (ST) * kWgImage * 4;                                             \
+    uint32_t m0_;                                                                                \
+    asm("s_nop 4\n\t"                                                                            \
+        "s_mov_b32 %0, m0\n\t"                                                                   \
+        "s_mov_b32 m0, %3\n\ts_nop 0\n\t"                                                        \
+        "global_load_lds_dwordx4 %2, %7\n\tglobal_load_lds_dwordx4 %2, %7 offset:1024\n\t"       \
+        "s_mov_b32 m0, %4\n\ts_nop 0\n\t"                                                        \
+        "global_load_lds_dwordx4 %2, %8\n\tglobal_load_lds_dwordx4 %2, %8 offset:1024\n\t"       \
+        "s_mov_b32 m0, %5\n\ts_nop 0\n\t"                                                        \
+        "global_load_lds_dwordx4 %2, %9\n\tglobal_load_lds_dwordx4 %2, %9 offset:1024\n\t"       \
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\t"                                                        \
+        "global_load_lds_dwordx4 %2, %10\n\tglobal_load_lds_dwordx4 %2, %10 offset:1024\n\t"     \
+        "s_mov_b32 m0, %0"                                                                       \
+        : "=&s"(m0_), "+v"(token)                                                                \
+        : "v"(u_lane), "s"(l_), "s"(l_ + kWgSlab * 4), "s"(l_ + 2 * kWgSlab * 4),                \
+          "s"(l_ + 3 * kWgSlab * 4), "s"(g_), "s"(g_ + u_pos), "s"(g_ + 2 * u_pos),              \
+          "s"(g_ + 3 * u_pos), "v"(after));                                                      \
+  } while (0)
+
+  // B^T d B of patch set S into V stage ST: columns first (e = B^T d), then rows, each V row
+  // written as soon as it is complete
+#define FRH_WG_Z(S, r, c) (xok[r][c] ? x##S##r##c : z2)
 #define FRH_WG_VROW(vp, e0, e1, e2, e3)                                   \
   do {                                                                    \
     *reinterpret_cast<wg_f32x2*>(vp) = (e0) - (e2);                       \
@@ -209,29 +267,22 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
     *reinterpret_cast<wg_f32x2*>((vp) + 2 * kWgSlab) = (e2) - (e1);       \
     *reinterpret_cast<wg_f32x2*>((vp) + 3 * kWgSlab) = (e1) - (e3);       \
   } while (0)
-#define FRH_WG_STORE(ST)                                                                             \
-  do {                                                                                               \
-    float* sp = lds + (ST) * kWgStage;                                                               \
-    float* uq = sp + u_off;                                                                          \
-    *reinterpret_cast<float4*>(uq) = u0, *reinterpret_cast<float4*>(uq + 2 * kWgSlab) = u1;          \
-    *reinterpret_cast<float4*>(uq + 4 * kWgSlab) = u2, *reinterpret_cast<float4*>(uq + 6 * kWgSlab) = u3;   \
-    *reinterpret_cast<float4*>(uq + 8 * kWgSlab) = u4, *reinterpret_cast<float4*>(uq + 10 * kWgSlab) = u5;  \
-    *reinterpret_cast<float4*>(uq + 12 * kWgSlab) = u6, *reinterpret_cast<float4*>(uq + 14 * kWgSlab) = u7; \
-    const wg_f32x2 z2 = {0.0f, 0.0f};                                                                \
-    const wg_f32x2 d00 = FRH_WG_Z(0, 0), d01 = FRH_WG_Z(0, 1), d02 = FRH_WG_Z(0, 2), d03 = FRH_WG_Z(0, 3); \
-    const wg_f32x2 d10 = FRH_WG_Z(1, 0), d11 = FRH_WG_Z(1, 1), d12 = FRH_WG_Z(1, 2), d13 = FRH_WG_Z(1, 3); \
-    const wg_f32x2 d20 = FRH_WG_Z(2, 0), d21 = FRH_WG_Z(2, 1), d22 = FRH_WG_Z(2, 2), d23 = FRH_WG_Z(2, 3); \
-    const wg_f32x2 d30 = FRH_WG_Z(3, 0), d31 = FRH_WG_Z(3, 1), d32 = FRH_WG_Z(3, 2), d33 = FRH_WG_Z(3, 3); \
-    float* vp = sp + v_off;                                                                          \
-    FRH_WG_VROW(vp, d00 - d20, d01 - d21, d02 - d22, d03 - d23);                                     \
-    FRH_WG_VROW(vp + 4 * kWgSlab, d10 + d20, d11 + d21, d12 + d22, d13 + d23);                       \
-    FRH_WG_VROW(vp + 8 * kWgSlab, d20 - d10, d21 - d11, d22 - d12, d23 - d13);                       \
-    FRH_WG_VROW(vp + 12 * kWgSlab, d10 - d30, d11 - d31, d12 - d32, d13 - d33);                      \
+#define FRH_WG_VSTORE(ST, S)                                                                               \
+  do {                                                                                                     \
+    const wg_f32x2 d00 = FRH_WG_Z(S, 0, 0), d01 = FRH_WG_Z(S, 0, 1), d02 = FRH_WG_Z(S, 0, 2), d03 = FRH_WG_Z(S, 0, 3); \
+    const wg_f32x2 d10 = FRH_WG_Z(S, 1, 0), d11 = FRH_WG_Z(S, 1, 1), d12 = FRH_WG_Z(S, 1, 2), d13 = FRH_WG_Z(S, 1, 3); \
+    const wg_f32x2 d20 = FRH_WG_Z(S, 2, 0), d21 = FRH_WG_Z(S, 2, 1), d22 = FRH_WG_Z(S, 2, 2), d23 = FRH_WG_Z(S, 2, 3); \
+    const wg_f32x2 d30 = FRH_WG_Z(S, 3, 0), d31 = FRH_WG_Z(S, 3, 1), d32 = FRH_WG_Z(S, 3, 2), d33 = FRH_WG_Z(S, 3, 3); \
+    float* vp = lds + (2 + (ST)) * kWgImage + v_off;                                                       \
+    FRH_WG_VROW(vp, d00 - d20, d01 - d21, d02 - d22, d03 - d23);                                           \
+    FRH_WG_VROW(vp + 4 * kWgSlab, d10 + d20, d11 + d21, d12 + d22, d13 + d23);                             \
+    FRH_WG_VROW(vp + 8 * kWgSlab, d20 - d10, d21 - d11, d22 - d12, d23 - d13);                             \
+    FRH_WG_VROW(vp + 12 * kWgSlab, d10 - d30, d11 - d31, d12 - d32, d13 - d33);                            \
   } while (0)
 
 #define FRH_WG_MFMA(ST, p)                                                          \
   do {                                                                              \
-    const float* sp = lds + (ST) * kWgStage + (p) * kWgSlab;                        \
+    const float* sp = lds + (ST) * kWgImage + (p) * kWgSlab;                        \
     const float4 av = *reinterpret_cast<const float4*>(sp + a_off);                 \
     const float4 bv = *reinterpret_cast<const float4*>(sp + b_off);                 \
     acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[p], 0, 0, 0);     \
@@ -240,39 +291,42 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
     acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[p], 0, 0, 0);     \
   } while (0)
 
-  // One chunk: its 64 MFMAs from stage ST; the next chunk (in registers since the last step)
-  // transformed into the other stage; the chunk after that loaded.  The other stage was last
-  // read one chunk ago, which every wave left before that step's barrier.  The stage is a
-  // literal so that the LDS reads and writes of a step are provably disjoint, and the
-  // scheduling groups spread the staging work over the MFMAs' issue gaps: per position the
-  // operand reads of the next one, then per MFMA two VALU and one memory instruction -- the U
-  // copy's LDS writes and the selects that free the staging registers first, the 24 loads of
-  // the chunk after next from the 17th MFMA on (most of a step ahead of their use), V's LDS
-  // writes last.
-#define FRH_WG_GROUPS(N, MEM, ID)                                                     \
+  // the step's DMA and patch loads landed, its LDS writes done, then the barrier
+#define FRH_WG_SYNC()                                                                        \
+  do {                                                                                       \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" : "+v"(token) : : "memory");    \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+  } while (0)
+
+  // One step: chunk t's 64 MFMAs from stage ST.  Beside them U of chunk t + 1 goes by DMA into
+  // the other U stage, the patch of chunk t + 2 is loaded into set ST, and the patch of chunk
+  // t + 1 (set ST ^ 1, loaded one step ago) is transformed into the other V stage.  That stage
+  // was last read one step ago, which every wave left before that step's barrier.  Past the
+  // last chunk the prefetches repeat the last chunk (valid addresses, nobody reads the result),
+  // so every step is this one body.  The stage is a literal so that the LDS reads and writes
+  // of a step are provably disjoint, and the scheduling groups spread the staging work over
+  // the MFMAs' issue gaps: per position the operand reads of the next one; in the first 8
+  // MFMAs four VALU (the selects that read the landed set) and two patch loads each, the DMA
+  // behind them; then two VALU per MFMA and V's LDS writes last.
+#define FRH_WG_GROUPS(N, VALU, MEM, K, ID)                                          \
   _Pragma("unroll") for (int p = 0; p < (N); ++p) {                                 \
     __builtin_amdgcn_sched_group_barrier(0x100, 2, ID);                             \
     _Pragma("unroll") for (int m = 0; m < 4; ++m) {                                 \
       __builtin_amdgcn_sched_group_barrier(0x008, 1, ID);                           \
-      __builtin_amdgcn_sched_group_barrier(0x002, 2, ID);                           \
-      __builtin_amdgcn_sched_group_barrier(MEM, 1, ID);                             \
+      __builtin_amdgcn_sched_group_barrier(0x002, VALU, ID);                        \
+      __builtin_amdgcn_sched_group_barrier(MEM, K, ID);                             \
     }                                                                               \
   }
-#define FRH_WG_STEP(ST, STORE, LOAD, t)                                             \
+#define FRH_WG_STEP(ST, OT, t)                                                        \
   do {                                                                              \
     _Pragma("unroll") for (int p = 0; p < 16; ++p) FRH_WG_MFMA(ST, p);              \
-    if (STORE) FRH_WG_STORE((ST) ^ 1);                                              \
-    if (LOAD) FRH_WG_LOAD((t) + 2);                                                 \
-    if (STORE) {                                                                    \
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, ST);                           \
-      FRH_WG_GROUPS(4, 0x200, ST);                                                     \
-      FRH_WG_GROUPS(6, 0x020, ST);                                                     \
-      FRH_WG_GROUPS(6, 0x200, ST);                                                     \
-    }                                                                               \
-    if (STORE) {                                                                    \
-      __syncthreads();                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                            \
-    }                                                                               \
+    FRH_WG_LOADX(ST, min((t) + 2, last));                                           \
+    FRH_WG_DMA(OT, min((t) + 1, last), FRH_WG_Z(OT, 3, 3).y);                       \
+    FRH_WG_VSTORE(OT, OT);                                                          \
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, ST);                             \
+    FRH_WG_GROUPS(2, 4, 0x020, 2, ST);                                              \
+    FRH_WG_GROUPS(14, 2, 0x200, 1, ST);                                             \
+    FRH_WG_SYNC();                                                                  \
   } while (0)
 
   wg_f32x16 acc[16];
@@ -281,34 +335,27 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[p][r] = 0.0f;
 
-  const int steps = a.cin / kWgBK;
-  FRH_WG_LOAD(0);
-  FRH_WG_STORE(0);
-  if (steps > 1) FRH_WG_LOAD(1);
-  __syncthreads();
-  int t = 0;
-  for (; t + 3 < steps; t += 2) {
-    FRH_WG_STEP(0, true, true, t);
-    FRH_WG_STEP(1, true, true, t + 1);
-  }
-  // one to three chunks left, t even
-  if (t + 3 == steps) {
-    FRH_WG_STEP(0, true, true, t);
-    FRH_WG_STEP(1, true, false, t + 1);
-    FRH_WG_STEP(0, false, false, t + 2);
-  } else if (t + 2 == steps) {
-    FRH_WG_STEP(0, true, false, t);
-    FRH_WG_STEP(1, false, false, t + 1);
-  } else {
-    FRH_WG_STEP(0, false, false, t);
+  const int last = a.cin / kWgBK - 1;
+  uint32_t token = 0;
+  FRH_WG_DMA(0, 0, 0.0f);
+  FRH_WG_LOADX(0, 0);
+  FRH_WG_LOADX(1, min(1, last));
+  FRH_WG_VSTORE(0, 0);
+  FRH_WG_SYNC();
+  for (int t = 0;; t += 2) {
+    FRH_WG_STEP(0, 1, t);
+    if (t >= last) break;
+    FRH_WG_STEP(1, 0, t + 1);
+    if (t + 1 >= last) break;
   }
 #undef FRH_WG_LX
-#undef FRH_WG_LU
-#undef FRH_WG_LOAD
+#undef FRH_WG_LOADX
+#undef FRH_WG_DMA
 #undef FRH_WG_Z
 #undef FRH_WG_VROW
-#undef FRH_WG_STORE
+#undef FRH_WG_VSTORE
 #undef FRH_WG_MFMA
+#undef FRH_WG_SYNC
 #undef FRH_WG_GROUPS
 #undef FRH_WG_STEP
 

@@ -1,6 +1,6 @@
 """Per-level timing of frh_conv3x3_bias_act against the path it replaces.
 
-    python tools/bench_conv3x3.py [--iters 20] [--out profiles/conv3x3/bench_conv3x3.json]
+    python tools/bench_conv3x3.py [--iters 20] [--out profiles/conv3x3/bench_conv3x3.json] [--fused-only]
 
 For the nine 3x3 / stride-1 / 256 -> 256 convolutions of the cfg2 neck and RPN head (2 images
 of 608 x 1024: P2 152x256, P3 76x128, P4 38x64, P5 19x32, P6 10x16; FPN form = bias, no ReLU,
@@ -66,6 +66,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'conv3x3', 'bench_conv3x3.json'))
+    ap.add_argument('--fused-only', action='store_true',
+                    help='time only the fused entries (no MIOpen side, no search): for counter passes')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_conv3x3 needs a HIP device')
@@ -106,10 +108,15 @@ def main():
                 else:
                     parent = [(lambda x=x: conv(x)) for x in xs]
                 sides = {'parent': parent, 'fused': [entry(x, y, relu) for x, y in zip(xs, ys)]}
+                if args.fused_only:
+                    del sides['parent']
                 med = measure(sides, args.iters)
-                ref = parent[0]()
-                sides['fused'][0]()
-                maxdiff = float((ref - ys[0]).abs().max() / ref.abs().max())
+                med.setdefault('parent', float('nan'))
+                maxdiff = float('nan')
+                if not args.fused_only:
+                    ref = parent[0]()
+                    sides['fused'][0]()
+                    maxdiff = float((ref - ys[0]).abs().max() / ref.abs().max())
                 flops = 2.0 * 16 * N * ((h + 1) // 2) * ((w + 1) // 2) * C * C
                 nbytes = 4.0 * (2 * N * h * w * C + 9 * C * C)
                 limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
@@ -147,8 +154,12 @@ def main():
             fs = [entry(all_x[k][i], y, True) for k, y in zip(names, outs[i])]
             return lambda: [f() for f in fs]
 
-        med = measure({'parent': [parent_all(i) for i in range(SETS)], 'levels': [levels_all(i) for i in range(SETS)],
-                       'per_level': [per_level_all(i) for i in range(SETS)]}, args.iters)
+        sides = {'parent': [parent_all(i) for i in range(SETS)], 'levels': [levels_all(i) for i in range(SETS)],
+                 'per_level': [per_level_all(i) for i in range(SETS)]}
+        if args.fused_only:
+            del sides['parent']
+        med = measure(sides, args.iters)
+        med.setdefault('parent', float('nan'))
         head = {k + '_us': round(v, 2) for k, v in med.items()}
         print('RPN head, five levels: parent {parent_us} us, one launch {levels_us} us, five launches {per_level_us} us'
               .format(**head), flush=True)
@@ -170,8 +181,11 @@ def main():
                  _lib.stream_of(xs[0]))
             return lambda: _lib.call('frh_conv3x3_bias_act_levels', *a)
 
-        med = measure({'parent': [fpn_parent(i) for i in range(SETS)], 'levels': [fpn_levels(i) for i in range(SETS)]},
-                      args.iters)
+        sides = {'parent': [fpn_parent(i) for i in range(SETS)], 'levels': [fpn_levels(i) for i in range(SETS)]}
+        if args.fused_only:
+            del sides['parent']
+        med = measure(sides, args.iters)
+        med.setdefault('parent', float('nan'))
         neck = {k + '_us': round(v, 2) for k, v in med.items()}
         print('FPN output convs, four levels: parent {parent_us} us, one launch {levels_us} us'.format(**neck),
               flush=True)
