@@ -5,7 +5,8 @@
 // torchvision legacy (aligned=False) RoIAlign semantics.
 //
 // Forward (all bit-identical: -ffp-contract=off, reference op order; kernels in
-// roi_kernels.h):
+// roi_kernels.h, each in the one form dispatched here; the template arguments roi_fwd picks are
+// slab sizes, waves per workgroup / SIMD and the span-timing build):
 //  * roi_align_fwd_cg_kernel -- channels-last features with C % 64 == 0 (the product trunk's
 //    FPN levels): one 4-wave workgroup per (RoI, 64 channels), the tap window staged once as
 //    [cell][64 channels] (256-B requests), lane = (bin, channel quad): bank-conflict-free
@@ -22,13 +23,17 @@
 //  * roi_align_fwd_lds_kernel -- odd channel counts: per-(RoI, 64 channels)
 //    workgroup, windows <= 256 floats staged in LDS, larger ones gathered.
 //  * roi_align_fwd_kernel -- direct gather, any pooled size / sampling ratio.
-// Backward: roi_align_bwd_sep_kernel (sampling 2, up to 8x8 bins: separable
-// row-run sums, one atomic per run) / roi_align_bwd_lds_kernel (up to 64 bins) /
+// Backward: roi_align_bwd_nhwc_kernel (channels-last gradients, sampling 2, up to 8x8 bins:
+// lane = channel, 4 waves per RoI) / roi_align_bwd_sep_kernel (sampling 2, up to 8x8 bins:
+// separable row-run sums, one atomic per run) / roi_align_bwd_lds_kernel (up to 64 bins) /
 // roi_align_bwd_kernel (per-tap atomics, any shape).
 // Feature tensors are addressed through explicit (batch, channel, y, x) element
 // strides: NCHW, channels_last and strided views (FPN P6 = P5[..., ::2, ::2]) all
-// run.  The forward laboratory (stamped builds, candidate kernels) is the tools-only
-// library (tools/csrc/roi_lab.hip).
+// run.  The laboratory -- these kernels at other slab sizes and wave counts, their stamped
+// builds, and the kernels measured and not adopted (tools/csrc/roi_lab_kernels.h) -- is the
+// tools-only library (tools/csrc/roi_lab.hip lists the variants; DESIGN.md §4 the results).
+// Lab variant numbers cited below that roi_lab.hip lists as retired were last built at commit
+// d6bef71.
 #include <hip/hip_ext.h>
 #include "roi_kernels.h"
 
@@ -38,8 +43,8 @@ namespace frh {
 // SIMD by registers): 8-row bands of the widest (29-column) windows, i.e. two bin rows of a
 // tap-list window per band; whole 1-KB LDS-DMA rounds (2 x 240 cells x 32 B of the interleaved
 // path and 15 rounds of 16 band cells both fill exactly 15 KB).  Windows of <= 192 cells take
-// the quad path (kHybrid = 4), <= 480 cells the two interleaved stages, larger ones the bands.
-// The bands' results are stored after the last band (kRot 3: whole channel rows per store).
+// the quad path (4 quads per stage), <= 480 cells the two interleaved stages, larger ones the bands.
+// The bands' results are stored after the last band (whole channel rows per store).
 // Measured (tools/bench_roi_sets.py, MI355X, µs per launch, bench / VOC / train-step RoIs):
 // this form 40.9 / 76.2 / 65.2 (stores per band: 40.9-42.9 / 77.2-79.0 / 67.2-69.3); bands
 // only 44.1-47.3 / 76-78 / 66-70; quad kernel (13 KB slab, pair order) 37.7-39.1 / 103-106 /
@@ -191,9 +196,9 @@ static int32_t roi_fwd(int32_t num_levels, const float* const* feats, const int3
     FRH_REQUIRE(total <= (int64_t)0x7fffffff - 7, "too many RoIs");
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
     if (span)
-      go(roi_align_fwd_cg_kernel<4, kCgCells, kCpolNT, true, 5, false>, grid, dim3(4 * kWave));
+      go(roi_align_fwd_cg_kernel<4, kCgCells, true, 5>, grid, dim3(4 * kWave));
     else
-      go(roi_align_fwd_cg_kernel<4, kCgCells, kCpolNT, false, 5, false>, grid, dim3(4 * kWave));
+      go(roi_align_fwd_cg_kernel<4, kCgCells, false, 5>, grid, dim3(4 * kWave));
   } else if (quad_ok(f, lv, channels, pooled_h, pooled_w) && band_fits(pooled_h, pooled_w, kBandCells)) {
     // channels-last features (the FPN's NHWC levels): one wave per (RoI, 16 channels); tap
     // windows of <= 192 cells staged whole, 4 quads at a time ([quad][cell]); <= 480 cells
@@ -202,30 +207,27 @@ static int32_t roi_fwd(int32_t num_levels, const float* const* feats, const int3
     const int64_t total = num_rois * ((channels + kQuadChunk - 1) / kQuadChunk);
     FRH_REQUIRE(total <= (int64_t)0x7fffffff - 7, "too many RoIs");
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
-    // kFwdTrim | kFwdIlvRot (round 6): no loads for lanes past the window and no empty DMA rounds;
-    // the interleaved path's two lanes of a cell read different quads at each step
-    constexpr int kOpt = kFwdTrim | kFwdIlvRot;
     if (span)
-      go(roi_align_fwd_band_kernel<kCpolNT, false, kBandCells, true, 3, 3, 4, 0, 2, 1, 1, kOpt>, grid, dim3(kWave));
+      go(roi_align_fwd_band_kernel<kBandCells, true>, grid, dim3(kWave));
     else
-      go(roi_align_fwd_band_kernel<kCpolNT, false, kBandCells, false, 3, 3, 4, 0, 2, 1, 1, kOpt>, grid, dim3(kWave));
+      go(roi_align_fwd_band_kernel<kBandCells, false>, grid, dim3(kWave));
   } else if (quad_ok(f, lv, channels, pooled_h, pooled_w)) {
     // channels-last, shapes the band kernel does not take: one quad per 16-B DMA lane
     const int64_t total = num_rois * ((channels + kQuadChunk - 1) / kQuadChunk);
     FRH_REQUIRE(total <= (int64_t)0x7fffffff - 7, "too many RoIs");
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
-    go(roi_align_fwd_quad_kernel<kCpolNT, false, 3>, grid, dim3(kWave));
+    go(roi_align_fwd_quad_kernel<>, grid, dim3(kWave));
   } else if (pair_ok(f, channels, pooled_h, pooled_w)) {
     // chunk-major XCD order, nt output stores, one 6.5 KB slab per wave, lean tap state
     const int64_t total = num_rois * ((channels + kPairChunk - 1) / kPairChunk);
     FRH_REQUIRE(total <= (int64_t)0x7fffffff - 7, "too many RoIs");
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
     if (span)
-      go(roi_align_fwd_pair_kernel<kCpolNT, false, true>, grid, dim3(kWave));
+      go(roi_align_fwd_pair_kernel<false, true>, grid, dim3(kWave));
     else
-      go(roi_align_fwd_pair_kernel<kCpolNT, false>, grid, dim3(kWave));
+      go(roi_align_fwd_pair_kernel<false, false>, grid, dim3(kWave));
   } else if (f.lds) {
-    go(roi_align_fwd_lds_kernel<256>, dim3((unsigned)num_rois, (unsigned)((channels + kRoiChanChunk - 1) / kRoiChanChunk)),
+    go(roi_align_fwd_lds_kernel, dim3((unsigned)num_rois, (unsigned)((channels + kRoiChanChunk - 1) / kRoiChanChunk)),
        dim3(kRoiThreads));
   } else {
     go(roi_align_fwd_kernel, dim3((unsigned)num_rois, (unsigned)((channels + kRoiChanChunk - 1) / kRoiChanChunk)),
@@ -263,7 +265,7 @@ extern "C" int32_t frh_roi_align_fwd_strided_timed(int32_t num_levels, const flo
 constexpr int kBwdWaves = 4;
 
 // channels-last gradient levels (unit channel stride), sampling 2, up to 8 x 8 bins: lane = channel
-static bool bwd_nhwc_ok(const RoiLevels& lv, int32_t sampling_ratio, int32_t ph, int32_t pw) {
+static bool bwd_lane_channel_ok(const RoiLevels& lv, int32_t sampling_ratio, int32_t ph, int32_t pw) {
   if (sampling_ratio != 2 || ph > 8 || pw > 8 || 4 * ph > kSepEnt || 4 * pw > kSepEnt) return false;
   for (int l = 0; l < lv.L; ++l)
     if (lv.sc[l] != 1) return false;
@@ -286,7 +288,7 @@ extern "C" int32_t frh_roi_align_bwd_strided(int32_t num_levels, float* const* g
   FRH_REQUIRE(grad_feats && grad_out, "null pointer argument");
   RoiCfg c{rois, roi_levels, num_rois, channels, pooled_h, pooled_w, sampling_ratio, aligned};
   dim3 grid((unsigned)num_rois, (unsigned)((channels + kRoiChanChunk - 1) / kRoiChanChunk));
-  if (bwd_nhwc_ok(lv, sampling_ratio, pooled_h, pooled_w))
+  if (bwd_lane_channel_ok(lv, sampling_ratio, pooled_h, pooled_w))
     hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, kBwdWaves>),
                        dim3((unsigned)num_rois, (unsigned)((channels + kWave - 1) / kWave)), dim3(kBwdWaves * kWave), 0,
                        as_stream(stream), lv, c, grad_out);
@@ -339,7 +341,7 @@ extern "C" int32_t frh_roi_align_bwd_fixed(int32_t num_levels, float* const* gra
     hipLaunchKernelGGL(roi_bwd_absmax_kernel, dim3((unsigned)mb), dim3(kAbsmaxThreads), 0, st, grad_out, ng,
                        scale_word);
     RoiCfg c{rois, roi_levels, num_rois, channels, pooled_h, pooled_w, sampling_ratio, aligned, nullptr, scale_word, hb};
-    if (bwd_nhwc_ok(lv, sampling_ratio, pooled_h, pooled_w)) {
+    if (bwd_lane_channel_ok(lv, sampling_ratio, pooled_h, pooled_w)) {
       hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<true, kBwdWaves>),
                          dim3((unsigned)num_rois, (unsigned)((channels + kWave - 1) / kWave)), dim3(kBwdWaves * kWave),
                          0, st, lv, c, grad_out);

@@ -36,8 +36,6 @@ struct RoiCfg {
   unsigned long long* span;  // measurement builds (kSpan): {min wave start, max wave end}, s_memrealtime
   const uint32_t* fix_max;   // fixed-point backward: bits of max|grad_out| (the call's own pass)
   int fix_hb;                // fixed-point backward: ceil(log2(K * ph * pw)), accumulation headroom
-  const int32_t* rec;        // forward, kFwdSorted: RoI records in processing order, 8 words each:
-                             // (x5 as written, level, original index, 0) -- roi_sort_kernel
 };
 
 // kSpan kernels: the launch's span on the 100 MHz clock, first wave start to last wave end.
@@ -113,8 +111,8 @@ __device__ __forceinline__ RoiGeom roi_geom(const RoiCfg& c, const RoiLevels& lv
 }
 
 // The RoI's box and level as loaded (RoiRaw), fetched by hand-issued scalar loads: the
-// compiler would wait for the level before loading the box, so the loads of one (or
-// two) RoIs go out together, followed by ONE lgkmcnt(0) wait (k wave-uniform).
+// compiler would wait for the level before loading the box, so the RoI's loads go out
+// together, followed by ONE lgkmcnt(0) wait (k wave-uniform).
 struct RoiRaw {
   float r0, r1, r2, r3, r4;
   int lvl;
@@ -143,42 +141,6 @@ __device__ __forceinline__ RoiRaw roi_fetch(const RoiCfg& c, int64_t k) {
       : "s"(c.rois + k * 5), "s"(roi_level_ptr(c, k))
       : "memory");
   return roi_raw(c, q, r4, l);
-}
-
-// record j of c.rec (kFwdSorted): the RoI and, in *ko, the output row it belongs to
-typedef uint32_t roi_u32x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ RoiRaw roi_fetch_rec(const RoiCfg& c, int64_t j, int64_t* ko) {
-  roi_u32x8_t q;
-  const uint64_t a = reinterpret_cast<uint64_t>(c.rec + j * 8);  // wave-uniform: made scalar
-  const uint64_t as = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-  asm volatile(
-      "s_load_dwordx8 %0, %1, 0x0\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=s"(q)
-      : "s"(reinterpret_cast<const int32_t*>(as))
-      : "memory");
-  *ko = (int64_t)q[6];
-  return RoiRaw{__uint_as_float(q[0]), __uint_as_float(q[1]), __uint_as_float(q[2]), __uint_as_float(q[3]),
-                __uint_as_float(q[4]), (int)q[5]};
-}
-
-__device__ __forceinline__ void roi_fetch2(const RoiCfg& c, int64_t k0, int64_t k1, RoiRaw* a, RoiRaw* b) {
-  roi_u32x4_t q0, q1;
-  uint32_t r40, r41, l0, l1;
-  asm volatile(
-      "s_load_dwordx4 %0, %6, 0x0\n\t"
-      "s_load_dword %1, %6, 0x10\n\t"
-      "s_load_dword %2, %7, 0x0\n\t"
-      "s_load_dwordx4 %3, %8, 0x0\n\t"
-      "s_load_dword %4, %8, 0x10\n\t"
-      "s_load_dword %5, %9, 0x0\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&s"(q0), "=&s"(r40), "=&s"(l0), "=&s"(q1), "=&s"(r41), "=&s"(l1)
-      : "s"(c.rois + k0 * 5), "s"(roi_level_ptr(c, k0)), "s"(c.rois + k1 * 5), "s"(roi_level_ptr(c, k1))
-      : "memory");
-  *a = roi_raw(c, q0, r40, l0);
-  *b = roi_raw(c, q1, r41, l1);
 }
 
 // roi_geom from a fetched RoI

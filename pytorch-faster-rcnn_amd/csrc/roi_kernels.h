@@ -1,5 +1,8 @@
-// RoIAlign kernels shared by the product library (csrc/roi_align.hip) and the
-// tools-only variant library (tools/csrc/roi_variants.hip).  See roi_align.hip.
+// RoIAlign kernels of the product library (csrc/roi_align.hip), each in its shipped form; the
+// template parameters left are those two product instantiations differ in and the measurement /
+// structural knobs (kSpan, kStamp, slab size, kWpe, kNW).  The tools-only laboratory
+// (tools/csrc/roi_lab.hip) instantiates them at other values of those knobs; kernels measured and
+// not adopted live in tools/csrc/roi_lab_kernels.h.  See roi_align.hip.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -85,10 +88,9 @@ static __global__ void __launch_bounds__(kRoiThreads) roi_align_fwd_kernel(RoiLe
 // a sample row are one 8-byte load: 8 loads per (bin, channel) instead of 16.
 // The 1/count of SR=2 is an exact power of two, so acc * 0.25 == acc / 4.
 // Results identical to the direct kernel.
-template <int U>
 __device__ __forceinline__ void fwd_buf_block(const RoiLevels& lv, const RoiCfg& c, float* __restrict__ out,
                                               int64_t k, int c0, const RoiGeom& g) {
-  constexpr int SR = 2;
+  constexpr int SR = 2, U = 2;  // U: channel steps per unrolled round
   const int l = g.lvl;
   const int H = lv.h[l], W = lv.w[l];
   const int nbins = c.ph * c.pw;
@@ -229,18 +231,15 @@ __device__ __forceinline__ void fwd_buf_block(const RoiLevels& lv, const RoiCfg&
 // holding a copy of the window's last feature column, so a right-border
 // clamped tap (x_lo = x_hi = W-1) reads (x_lo, x_lo + 1) like every other
 // sample.  No block barriers: waves are independent.  Windows above
-// kWinMax floats take the per-wave gather path.  Results identical to the
+// kStageMax floats take the block gather path.  Results identical to the
 // direct kernel.
-constexpr int kWinMax = 1024;
+constexpr int kWinMax = 1024;  // floats per wave slab
 constexpr int kWinR = kWinMax / kWave;
+constexpr int kStageMax = 256;  // largest staged window (floats)
 
-// kChunk: channels per workgroup (kChunk / 4 per wave).
-// kWpe: minimum waves per SIMD the register allocation must allow (0: compiler's choice).
-template <int kStageMax, int kChunk = kRoiChanChunk, int kWpe = 0>
-__global__ void __launch_bounds__(kRoiThreads) __attribute__((amdgpu_waves_per_eu(kWpe > 0 ? kWpe : 1)))
-roi_align_fwd_lds_kernel(RoiLevels lv, RoiCfg c,
-                                                                        float* __restrict__ out) {
-  constexpr int SR = 2;
+static __global__ void __launch_bounds__(kRoiThreads) __attribute__((amdgpu_waves_per_eu(1)))
+roi_align_fwd_lds_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
+  constexpr int SR = 2, kChunk = kRoiChanChunk;  // kChunk: channels per workgroup (kChunk / 4 per wave)
   __shared__ float slab_all[kRoiThreads / kWave][kWinMax];
   const int64_t k = blockIdx.x;
   // readfirstlane: the wave index is uniform, and the compiler must know it (soffset operands)
@@ -270,8 +269,8 @@ roi_align_fwd_lds_kernel(RoiLevels lv, RoiCfg c,
   // odd slab row stride: the 4 tap rows of a wave's bins spread over the LDS banks
   const int ws = (x1 - x0 + 2) | 1, n = any ? (y1 - y0 + 1) * ws : 0;
   if (n > kStageMax) {  // uniform over the block (one RoI): large windows take the block gather path
-    for (int cc = 0; cc < kChunk && blockIdx.y * kChunk + cc < c.C; cc += kRoiChanChunk)
-      fwd_buf_block<2>(lv, c, out, k, blockIdx.y * kChunk + cc, g);
+    for (int cc = 0; cc < kChunk && blockIdx.y * kChunk + cc < c.C; cc += kRoiChanChunk)  // one trip
+      fwd_buf_block(lv, c, out, k, blockIdx.y * kChunk + cc, g);
     return;
   }
   if (nch <= 0) return;
@@ -315,84 +314,79 @@ roi_align_fwd_lds_kernel(RoiLevels lv, RoiCfg c,
     return acc * 0.25f;
   };
   const bool active = lane < nbins;
-  if (n <= kStageMax) {
-    // slab addresses of this bin's sample rows (x_lo, x_lo + 1 pairs)
-    int sa[SR][2][SR];
+  // slab addresses of this bin's sample rows (x_lo, x_lo + 1 pairs)
+  int sa[SR][2][SR];
 #pragma unroll
-    for (int iy = 0; iy < SR; ++iy)
+  for (int iy = 0; iy < SR; ++iy)
 #pragma unroll
-      for (int ix = 0; ix < SR; ++ix) {
-        const bool v = ok[iy][ix];
-        sa[iy][0][ix] = v ? (ty[iy].lo - y0) * ws + (tx[ix].lo - x0) : 0;
-        sa[iy][1][ix] = v ? (ty[iy].hi - y0) * ws + (tx[ix].lo - x0) : 0;
-      }
-    // staging: slab element e = lane + 64 j  <-  feature (y0 + e / ws, min(x0 + e % ws, W - 1));
-    // the j loop is specialised on RB = 64-element rounds (1, 2, 4, 8, 16) so it unrolls branch-free
-    auto run = [&](auto rb) {
-      constexpr int RB = decltype(rb)::value, D = kWinR / RB;  // D channel windows per round, 16 loads/lane
-      int goff[RB];
+    for (int ix = 0; ix < SR; ++ix) {
+      const bool v = ok[iy][ix];
+      sa[iy][0][ix] = v ? (ty[iy].lo - y0) * ws + (tx[ix].lo - x0) : 0;
+      sa[iy][1][ix] = v ? (ty[iy].hi - y0) * ws + (tx[ix].lo - x0) : 0;
+    }
+  // staging: slab element e = lane + 64 j  <-  feature (y0 + e / ws, min(x0 + e % ws, W - 1));
+  // the j loop is specialised on RB = 64-element rounds (1, 2, 4 = kStageMax / 64) so it unrolls branch-free
+  auto run = [&](auto rb) {
+    constexpr int RB = decltype(rb)::value, D = kWinR / RB;  // D channel windows per round, 16 loads/lane
+    int goff[RB];
 #pragma unroll
-      for (int j = 0; j < RB; ++j) {
-        const int e = lane + j * kWave;
-        const int r = e / ws, cc = e - r * ws;
-        // lanes past the window re-read its first element: no extra cache line per round
-        goff[j] = e < n ? ((y0 + r) * sy + min(x0 + cc, W - 1) * sx) * 4 : (y0 * sy + x0 * sx) * 4;
-      }
-      float st[D][RB];
-      auto issue = [&](int c0r) {
+    for (int j = 0; j < RB; ++j) {
+      const int e = lane + j * kWave;
+      const int r = e / ws, cc = e - r * ws;
+      // lanes past the window re-read its first element: no extra cache line per round
+      goff[j] = e < n ? ((y0 + r) * sy + min(x0 + cc, W - 1) * sx) * 4 : (y0 * sy + x0 * sx) * 4;
+    }
+    float st[D][RB];
+    auto issue = [&](int c0r) {
 #pragma unroll
-        for (int d = 0; d < D; ++d)
+      for (int d = 0; d < D; ++d)
 #pragma unroll
-          for (int j = 0; j < RB; ++j)
-            st[d][j] = __uint_as_float(
-                __builtin_amdgcn_raw_buffer_load_b32(fr, goff[j], min(c0r + d, nch - 1) * cstep, 0));
-      };
-      issue(0);
-      for (int i = 0; i < nch; i += D) {
+        for (int j = 0; j < RB; ++j)
+          st[d][j] = __uint_as_float(
+              __builtin_amdgcn_raw_buffer_load_b32(fr, goff[j], min(c0r + d, nch - 1) * cstep, 0));
+    };
+    issue(0);
+    for (int i = 0; i < nch; i += D) {
 #pragma unroll
-        for (int d = 0; d < D; ++d)
+      for (int d = 0; d < D; ++d)
 #pragma unroll
-          for (int j = 0; j < RB; ++j) slab[(d * RB + j) * kWave + lane] = st[d][j];  // [n, 64 RB) junk, unread
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (i + D < nch) issue(i + D);
-        if (active) {
+        for (int j = 0; j < RB; ++j) slab[(d * RB + j) * kWave + lane] = st[d][j];  // [n, 64 RB) junk, unread
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (i + D < nch) issue(i + D);
+      if (active) {
 #pragma unroll
-          for (int d = 0; d < D; ++d) {
-            if (i + d < nch) {
-              const float* sl = slab + d * RB * kWave;
-              float v[SR][SR][4];
+        for (int d = 0; d < D; ++d) {
+          if (i + d < nch) {
+            const float* sl = slab + d * RB * kWave;
+            float v[SR][SR][4];
 #pragma unroll
-              for (int iy = 0; iy < SR; ++iy)
+            for (int iy = 0; iy < SR; ++iy)
 #pragma unroll
-                for (int ix = 0; ix < SR; ++ix) {
-                  v[iy][ix][0] = sl[sa[iy][0][ix]];
-                  v[iy][ix][1] = sl[sa[iy][0][ix] + 1];
-                  v[iy][ix][2] = sl[sa[iy][1][ix]];
-                  v[iy][ix][3] = sl[sa[iy][1][ix] + 1];
-                }
-              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bin_value(v)), orr, lane * 4, (i + d) * ostep, 0);
-            }
+              for (int ix = 0; ix < SR; ++ix) {
+                v[iy][ix][0] = sl[sa[iy][0][ix]];
+                v[iy][ix][1] = sl[sa[iy][0][ix] + 1];
+                v[iy][ix][2] = sl[sa[iy][1][ix]];
+                v[iy][ix][3] = sl[sa[iy][1][ix] + 1];
+              }
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bin_value(v)), orr, lane * 4, (i + d) * ostep, 0);
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
-    };
-    const int R = (n + kWave - 1) / kWave;
-    if (R <= 1)
-      run(std::integral_constant<int, 1>{});
-    else if (R <= 2 || kStageMax <= 2 * kWave)
-      run(std::integral_constant<int, 2>{});
-    else if (R <= 4 || kStageMax <= 4 * kWave)
-      run(std::integral_constant<int, 4>{});
-    else if (R <= 8 || kStageMax <= 8 * kWave)
-      run(std::integral_constant<int, 8>{});
-    else
-      run(std::integral_constant<int, kWinR>{});
-  }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  };
+  const int R = (n + kWave - 1) / kWave;
+  static_assert(kStageMax == 4 * kWave, "the rounds below");
+  if (R <= 1)
+    run(std::integral_constant<int, 1>{});
+  else if (R <= 2)
+    run(std::integral_constant<int, 2>{});
+  else
+    run(std::integral_constant<int, 4>{});
 }
 
 
@@ -451,9 +445,9 @@ __device__ __forceinline__ void lds_wait(f32x2 (&v)[8]) {
                : "memory");
 }
 
-template <int D, int kHalf = kPairHalf>
+template <int D>
 struct PairLayout {
-  static constexpr int RS = (kHalf / D) / kWave * kWave;  // dwords per pair region
+  static constexpr int RS = (kPairHalf / D) / kWave * kWave;  // dwords per pair region
   static constexpr int RP = RS / kWave;                       // DMA rounds per pair
   static constexpr int kCells = RS / 2;
   static_assert(D * RP + 2 * D < 64, "vmcnt is 6 bits");
@@ -558,14 +552,14 @@ __device__ __forceinline__ void pair_setup(const RoiLevels& lv, const RoiCfg& c,
   G.inv = (65536u + (uint32_t)G.Cs2 - 1u) / (uint32_t)G.Cs2;
 }
 
-// One item: RoI k, channel chunk `chunk` (16 channels).  kStAux / kLdAux: cache policy
-// of the output stores / staging loads (cdna.h).  kStamp (tools-only timing builds):
+// One item: RoI k, channel chunk `chunk` (16 channels).  Output stores nontemporal (kCpolNT),
+// staging loads with the default policy (cdna.h).  kStamp (tools-only timing builds):
 // lane 0 writes 8 int64 per item after the output -- s_memrealtime at start / setup
 // done / first stage landed / end, D, cells, RoI record landed, XCD.
-template <int kStAux, int kLdAux, bool kStamp>
+template <bool kStamp>
 __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, float* __restrict__ out, int64_t k,
                                           int chunk, int64_t item, uint32_t sbase, int64_t t_start, int lane) {
-  constexpr int SR = 2, kPW = kPairWave, kHalf = kPairHalf;
+  constexpr int SR = 2, kPW = kPairWave, kStAux = kCpolNT;
   int64_t t_setup = 0, t_land = 0, t_fetched = 0;
   const int cw0 = chunk * 2 * kPW;
   const int npairs = min(kPW, (c.C - cw0) / 2);  // host: C even
@@ -586,7 +580,7 @@ __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, 
   const int y0 = G.y0, x0 = G.x0, R = G.R, Cs = G.Cs, Cs2 = G.Cs2, sy = G.sy, sx = G.sx, scs = G.scs;
   const bool dy = G.dy, dx = G.dx;
   const int ncell = R * Cs2;
-  const bool small = ncell <= PairLayout<8, kHalf>::kCells;
+  const bool small = ncell <= PairLayout<8>::kCells;
   const int rsrc = P.rsrc, csrc = P.csrc;
   const __amdgpu_buffer_rsrc_t fr = uniform_rsrc(G.base, (int64_t)G.extent);
   const uint32_t inv = G.inv;
@@ -594,7 +588,7 @@ __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, 
   int stamp_d = 0;
 
   auto run = [&](auto dd) {
-    constexpr int D = decltype(dd)::value, RS = PairLayout<D, kHalf>::RS, RP = PairLayout<D, kHalf>::RP;
+    constexpr int D = decltype(dd)::value, RS = PairLayout<D>::RS, RP = PairLayout<D>::RP;
     const int nst = (npairs + D - 1) / D;
     // region dword j * 64 + lane of every pair  <-  channel (lane & 1) of cell (j * 64 + lane) / 2
     auto goff_at = [&](int j) {
@@ -613,7 +607,7 @@ __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, 
       for (int d = 0; d < D; ++d) {
         const int soff = (cw0 + 2 * min(s * D + d, npairs - 1)) * scs * 4;
 #pragma unroll
-        for (int j = 0; j < RP; ++j) lds_dma_at<4, kLdAux>(fr, sbase + 4u * (uint32_t)(d * RS + j * kWave), goff[j], soff);
+        for (int j = 0; j < RP; ++j) lds_dma_at<4, 0>(fr, sbase + 4u * (uint32_t)(d * RS + j * kWave), goff[j], soff);
       }
     };
     auto eval = [&](int s) {
@@ -687,9 +681,9 @@ __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, 
   };
   if (small)
     run(std::integral_constant<int, 8>{});
-  else if (ncell <= PairLayout<4, kHalf>::kCells)
+  else if (ncell <= PairLayout<4>::kCells)
     run(std::integral_constant<int, 4>{});
-  else if (ncell <= PairLayout<2, kHalf>::kCells)
+  else if (ncell <= PairLayout<2>::kCells)
     run(std::integral_constant<int, 2>{});
   else
     run(std::integral_constant<int, 1>{});
@@ -711,7 +705,7 @@ __device__ __forceinline__ void pair_item(const RoiLevels& lv, const RoiCfg& c, 
 // (= linear id % 8) takes the x-th eighth of the chunk-major (chunk, RoI) item list,
 // so each XCD's L2 holds the feature planes of its own channel chunks.  32-bit item
 // arithmetic (host: K * chunks < 2^31).
-template <int kStAux = kCpolNT, bool kStamp = false, bool kSpan = false>
+template <bool kStamp = false, bool kSpan = false>
 __global__ void __launch_bounds__(kWave) roi_align_fwd_pair_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
   const int64_t t_start = (kStamp || kSpan) ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
   __shared__ __attribute__((aligned(16))) float slab[kPairHalf];
@@ -724,7 +718,7 @@ __global__ void __launch_bounds__(kWave) roi_align_fwd_pair_kernel(RoiLevels lv,
   if (w >= wend) return;
   const int ch0 = (int)(w / K32);
   const int64_t k0 = (int64_t)(w - (uint32_t)ch0 * K32);
-  pair_item<kStAux, 0, kStamp>(lv, c, out, k0, ch0, w, sbase, t_start, threadIdx.x & (kWave - 1));
+  pair_item<kStamp>(lv, c, out, k0, ch0, w, sbase, t_start, threadIdx.x & (kWave - 1));
   if (kSpan && threadIdx.x == 0) record_span(c, t_start);
 }
 
@@ -785,42 +779,20 @@ __device__ __forceinline__ f32x4 quad_val(const float (&w)[4], const f32x4* x) {
   return f32x4{lo.x, lo.y, hi.x, hi.y};
 }
 
-// kQW: channel quads per item (4: 16 channels).  kOut: 0 = per-channel 4-B stores of the
-// bin row (lane = bin), 1 = [channel][bin] staged in LDS (obuf), then 16-B stores of the
-// item's contiguous output block, 2 = no stores (tools-only diagnostic).
-// kOpt bit 1 (kFwdTrim): lanes past the window's cells load nothing (an out-of-range offset:
-// no memory request) and DMA rounds past the window are not issued.
-// kOpt bit 4 (kFwdSorted, tools-only experiment): item k reads record k of c.rec (a spatial
-// processing order, tools/csrc/roi_lab_kernels.h roi_sort_kernel) and writes the output row the
-// record names.
-constexpr int kFwdTrim = 1, kFwdIlvRot = 2, kFwdSorted = 4;
-template <int kStAux, bool kStamp, int kQW = kQuadWave, int kOut = 0, int kSlab = kQuadSlab, bool kOnly4 = false,
-          int kOpt = 0>
+// The item (RoI k, the 16 channels of `chunk`) after its setup (G, P of pair_setup<16>): staging,
+// evaluation, per-channel 4-B nontemporal stores of the bin row (lane = bin).  The host admits
+// only shapes whose largest tap grid fits one region (quad_ok: quad_max_cells <= kCells of D = 1).
+// kOnly4: the caller took ncell <= kCells of D = 4 (the band kernel's small windows).
+// kTrim (the band kernel's call): lanes past the window's cells load nothing (an out-of-range
+// offset: no memory request) and DMA rounds past the window are not issued.
+template <bool kStamp, int kSlab, bool kOnly4, bool kTrim>
 __device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, const RoiCfg& c,
                                           float* __restrict__ out, int64_t k, int chunk, int64_t item, uint32_t sbase,
-                                          int64_t t_start, int lane, float* obuf);
-
-template <int kStAux, bool kStamp, int kQW = kQuadWave, int kOut = 0, int kSlab = kQuadSlab>
-__device__ __forceinline__ void quad_item(const RoiLevels& lv, const RoiCfg& c, float* __restrict__ out, int64_t k,
-                                          int chunk, int64_t item, uint32_t sbase, int64_t t_start, int lane,
-                                          float* obuf = nullptr) {
-  PairGeom G;
-  PairLane P;
-  const RoiRaw raw = roi_fetch(c, k);
-  pair_setup<16>(lv, c, raw, lane, G, P);
-  quad_body<kStAux, kStamp, kQW, kOut, kSlab>(G, P, c, out, k, chunk, item, sbase, t_start, lane, obuf);
-}
-
-// the item after its setup (G, P): staging, evaluation, stores.  The host admits only
-// shapes whose largest tap grid fits one region (quad_ok: quad_max_cells <= kCells of D = 1).
-template <int kStAux, bool kStamp, int kQW, int kOut, int kSlab, bool kOnly4, int kOpt>
-__device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, const RoiCfg& c,
-                                          float* __restrict__ out, int64_t k, int chunk, int64_t item, uint32_t sbase,
-                                          int64_t t_start, int lane, float* obuf) {
-  constexpr int SR = 2;
+                                          int64_t t_start, int lane) {
+  constexpr int SR = 2, kStAux = kCpolNT;
   int64_t t_setup = 0, t_land = 0;
-  const int cw0 = chunk * 4 * kQW;
-  const int nquads = min(kQW, (c.C - cw0) / 4);  // host: C % 4 == 0
+  const int cw0 = chunk * kQuadChunk;
+  const int nquads = min(kQuadWave, (c.C - cw0) / 4);  // host: C % 4 == 0
   const int nbins = c.ph * c.pw;
   const bool active = lane < nbins;
   const __amdgpu_buffer_rsrc_t orr = uniform_rsrc(out + (k * c.C + cw0) * nbins, (int64_t)4 * nquads * nbins * 4);
@@ -839,19 +811,6 @@ __device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, 
   if (kStamp) t_setup = (int64_t)__builtin_amdgcn_s_memrealtime();
   int stamp_d = 0;
   auto store4 = [&](int q, f32x4 r) {
-    if constexpr (kOut == 2) {
-      if (r.x == 1234.5f) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r.y), orr, ovoff, 0, kStAux);
-      return;
-    }
-    if constexpr (kOut == 1) {
-      if (q < nquads && active) {
-        obuf[(4 * q) * nbins + lane] = r.x;
-        obuf[(4 * q + 1) * nbins + lane] = r.y;
-        obuf[(4 * q + 2) * nbins + lane] = r.z;
-        obuf[(4 * q + 3) * nbins + lane] = r.w;
-      }
-      return;
-    }
     const int vo = q < nquads ? ovoff : 0x40000000;
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r.x), orr, vo, (4 * q) * ostep, kStAux);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r.y), orr, vo, (4 * q + 1) * ostep, kStAux);
@@ -868,12 +827,12 @@ __device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, 
       e = in ? e : 0;
       const int r = (int)(((uint32_t)e * inv) >> 16), col = min(e - r * Cs2, Cs - 1);
       const int o = (dy && dx) ? ((y0 + r) * sy + (x0 + col) * sx) * 4 : __shfl(rsrc, r, kWave) + __shfl(csrc, col, kWave);
-      return ((kOpt & kFwdTrim) && !in) ? 0x40000000 : o;
+      return (kTrim && !in) ? 0x40000000 : o;
     };
     int goff[RP];
 #pragma unroll
     for (int j = 0; j < RP; ++j) goff[j] = goff_at(j);
-    const int nr = (kOpt & kFwdTrim) ? (ncell + kWave - 1) / kWave : RP;  // rounds holding cells (uniform)
+    const int nr = kTrim ? (ncell + kWave - 1) / kWave : RP;  // rounds holding cells (uniform)
     auto issue = [&](int s) {  // quads past the last re-read it (their stores are dropped)
 #pragma unroll
       for (int d = 0; d < D; ++d) {
@@ -951,19 +910,6 @@ __device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, 
     else  // ncell <= quad_max_cells(ph, pw) <= QuadLayout<1, kSlab>::kCells (quad_ok)
       run(std::integral_constant<int, 1>{});
   }
-  if constexpr (kOut == 1) {  // the item's [channel][bin] block: contiguous, 16-B stores
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int n4 = 4 * nquads * nbins / 4;
-    const float4* o4 = reinterpret_cast<const float4*>(obuf);
-    for (int e = lane; e < n4; e += kWave) {
-      const float4 q = o4[e];
-      __builtin_amdgcn_raw_buffer_store_b128(
-          u32x4{__float_as_uint(q.x), __float_as_uint(q.y), __float_as_uint(q.z), __float_as_uint(q.w)}, orr, e * 16,
-          0, kStAux);
-    }
-  }
   if (kStamp && lane == 0) {
     int64_t* st = reinterpret_cast<int64_t*>(out + c.K * c.C * nbins) + item * 8;
     const int64_t t_end = (int64_t)__builtin_amdgcn_s_memrealtime();
@@ -978,40 +924,31 @@ __device__ __forceinline__ void quad_body(const PairGeom& G, const PairLane& P, 
   }
 }
 
+template <bool kStamp, int kSlab>
+__device__ __forceinline__ void quad_item(const RoiLevels& lv, const RoiCfg& c, float* __restrict__ out, int64_t k,
+                                          int chunk, int64_t item, uint32_t sbase, int64_t t_start, int lane) {
+  PairGeom G;
+  PairLane P;
+  const RoiRaw raw = roi_fetch(c, k);
+  pair_setup<16>(lv, c, raw, lane, G, P);
+  quad_body<kStamp, kSlab, false, false>(G, P, c, out, k, chunk, item, sbase, t_start, lane);
+}
+
 // 1-D grid of 8 * ceil(K * chunks / 8) single-wave workgroups; XCD x takes the x-th eighth
-// of the item list (as the pair kernel: the two 16-channel chunks of a 128-B line share an
-// XCD).  kOrder 0: chunk-major (chunk, RoI); 1: chunk-pair-major, the pair's two chunks of
-// a RoI adjacent (2p, k), (2p + 1, k) -- the two waves reading the two halves of the same
-// lines run together, so the second finds them in L2.
-template <int kStAux = kCpolNT, bool kStamp = false, int kWpe = 3, int kQW = kQuadWave, int kOut = 0,
-          bool kSpan = false, int kSlab = kQuadSlab, int kOrder = 0>
+// of the chunk-major (chunk, RoI) item list (as the pair kernel).
+template <bool kStamp = false, int kWpe = 3, int kSlab = kQuadSlab>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWpe))) roi_align_fwd_quad_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
-  const int64_t t_start = (kStamp || kSpan) ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
+  const int64_t t_start = kStamp ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
   __shared__ __attribute__((aligned(16))) float slab[kSlab];
-  __shared__ __attribute__((aligned(16))) float obuf[kOut == 1 ? 4 * kQW * kWave : 4];  // [channel][bin], <= 64 bins
   const uint32_t sbase = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)slab);
-  const uint32_t G = (uint32_t)(c.C + 4 * kQW - 1) / (uint32_t)(4 * kQW), K32 = (uint32_t)c.K;
+  const uint32_t G = (uint32_t)(c.C + kQuadChunk - 1) / (uint32_t)kQuadChunk, K32 = (uint32_t)c.K;
   const uint32_t total = K32 * G, per = (total + 7u) / 8u;
   const uint32_t w = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
   const uint32_t wend = min((blockIdx.x & 7u) * per + per, total);
   if (w >= wend) return;
-  int ch0;
-  int64_t k0;
-  if (kOrder == 0) {
-    ch0 = (int)(w / K32);
-    k0 = (int64_t)(w - (uint32_t)ch0 * K32);
-  } else {
-    const uint32_t p = w / (2u * K32), r = w - p * 2u * K32;
-    if (2u * p + 1u < G) {
-      ch0 = (int)(2u * p + (r & 1u));
-      k0 = (int64_t)(r >> 1);
-    } else {  // odd chunk count: the last chunk alone
-      ch0 = (int)(2u * p);
-      k0 = (int64_t)r;
-    }
-  }
-  quad_item<kStAux, kStamp, kQW, kOut, kSlab>(lv, c, out, k0, ch0, w, sbase, t_start, threadIdx.x & (kWave - 1), obuf);
-  if (kSpan && threadIdx.x == 0) record_span(c, t_start);
+  const int ch0 = (int)(w / K32);
+  const int64_t k0 = (int64_t)(w - (uint32_t)ch0 * K32);
+  quad_item<kStamp, kSlab>(lv, c, out, k0, ch0, w, sbase, t_start, threadIdx.x & (kWave - 1));
 }
 
 // ---------------------------------------------------------------------------
@@ -1025,37 +962,30 @@ __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWpe
 // than the slab is staged in row bands: each band holds the rows of the next bin rows
 // whose samples fit (rows of the lowest pending bin first; every bin's rows span <= 5
 // <= kSlabCells / 29), evaluated by the lanes (bins) of those rows; windows within the slab
-// are one band (the random-init RoIs of the bench: all of them).  Tap reads: lane l reads
-// quad (d + l) mod 4 at step d, so the 16 lanes of a ds_read_b128 group spread over the
-// 64 banks (a fixed quad would put them on the 4 bank groups of cell mod 4); its stores
-// go to those quads' channels.  Same operation order per output: bit-identical to the
-// other kernels.
-template <int kSlabCells>
-struct BandLayout {
-  static_assert(kSlabCells % 16 == 0, "whole 16-cell DMA instructions");
-  static constexpr int kMaxDma = kSlabCells / 16;
-  static_assert(kMaxDma < 64, "vmcnt is 6 bits");
-};
+// are one band (the random-init RoIs of the bench: all of them).  Every lane reads quad d at
+// step d; the results are kept until the last band and stored by every bin at once (whole
+// channel rows per store; a band's own stores would cover only its bins' part of each row).
+// Same operation order per output: bit-identical to the other kernels.
+// Measured and rejected: lane l reading quad (d + l) mod 4 with the results in an
+// indexed per-bin array spilled to scratch (568 us); stores per band 40.9-42.9 / 77.2-79.0 /
+// 67.2-69.3 us against 40.9 / 76.2 / 65.2 (bench / VOC / train RoIs).
 
-// kRot: 0 = every lane reads quad d at step d (bank conflicts: 4 bank groups per quad);
-// 1 = lane l reads quad (d + l) mod 4, results kept and stored per channel after the 4 steps
-// (each store instruction writes one channel plane, 49 contiguous floats); 2 = as 1 but
-// each step's quad stored at once (lane-dependent channel planes: 4 partial lines each);
-// 3 = as 0, the results kept until the last band and stored by every bin at once (a band's
-// own stores cover only its bins' part of each channel row: partial lines).
 // Whole-window stages of two channel quads, cell-interleaved: the slab holds [cell][2 quads]
 // (32 B per cell), the two lanes of a cell read its 32 contiguous bytes (one request for two
 // quads, the quad layout's [quad][cell] takes two), quads {0, 1} then {2, 3}.  G / P carry the
 // quad layout's 16-B tap offsets (pair_setup<16>); every lane evaluates every stage (no band
 // masking) and stores whole channel rows.  For windows of up to kSlabCells * 2 cells.
-// kOpt bit 2 (kFwdIlvRot, D = 2): at step d lane l reads quad (d + l) & 1 of its cells, so the
-// 16 lanes of a ds_read_b128 group use both 16-B halves of the 32-B cells (16 bank slots
-// instead of 8); the two results are stored per channel after both steps.
-template <int kStAux, int kSlabCells, int D = 2, bool kStamp = false, int kOpt = 0>
+// At step d lane l reads quad (d + l) & 1 of its cells, so the 16 lanes of a ds_read_b128 group
+// use both 16-B halves of the 32-B cells (16 bank slots instead of 8); the two results are
+// stored per channel after both steps.  Lanes past the window's cells load nothing (an
+// out-of-range offset: no memory request).
+// Measured and rejected: one [cell][4 quads] stage for windows <= 232 cells
+// (bench 46 us: the quad layout's 64 cells per instruction beat 16 cells of 64 B there).
+template <bool kStamp>
 __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, const RoiCfg& c,
                                           float* __restrict__ out, int64_t k, int chunk, uint32_t sbase, int lane,
-                                          int64_t item = 0, int64_t t_start = 0) {
-  constexpr int SR = 2;
+                                          int64_t item, int64_t t_start) {
+  constexpr int SR = 2, D = 2, kStAux = kCpolNT;  // D: quads per stage
   const int cw0 = chunk * 4 * kQuadWave;
   const int nquads = min(kQuadWave, (c.C - cw0) / 4);  // host: C % 4 == 0
   const int nbins = c.ph * c.pw;
@@ -1066,7 +996,7 @@ __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, c
   const int y0 = G.y0, x0 = G.x0, Cs = G.Cs, Cs2 = G.Cs2, sy = G.sy, sx = G.sx;
   const bool dense = G.dy && G.dx;
   const int ncell = G.R * Cs2;
-  constexpr int kLg = D == 4 ? 2 : 1;
+  constexpr int kLg = 1;  // log2(D)
   const int nj = (ncell + (kWave / D - 1)) >> (6 - kLg);  // 64 / D cells per DMA instruction
   const __amdgpu_buffer_rsrc_t fr = uniform_rsrc(G.base, (int64_t)G.extent);
   const uint32_t inv = G.inv;
@@ -1079,7 +1009,7 @@ __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, c
       e = in ? e : 0;
       const int r = (int)(((uint32_t)e * inv) >> 16), col = min(e - r * Cs2, Cs - 1);
       const int goff = dense ? ((y0 + r) * sy + (x0 + col) * sx) * 4 : __shfl(P.rsrc, r, kWave) + __shfl(P.csrc, col, kWave);
-      lds_dma_at<16, 0>(fr, sbase + 1024u * (uint32_t)j, ((kOpt & kFwdTrim) && !in) ? 0x40000000 : goff + dq * 16, soff);
+      lds_dma_at<16, 0>(fr, sbase + 1024u * (uint32_t)j, in ? goff + dq * 16 : 0x40000000, soff);
     }
     wait_vmcnt<0>();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1102,17 +1032,16 @@ __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, c
     auto tap = [&](int iy, int ix, int q) -> uint32_t {
       return lb[iy][ix] + ((q & 1) ? ldq[ix] : 0u) + ((q & 2) ? ldr[iy] : 0u);
     };
-    constexpr bool kRotI = (kOpt & kFwdIlvRot) != 0 && D == 2;
-    f32x4 rr0 = {}, rr1 = {};  // kRotI: the results of steps 0 / 1
+    f32x4 rr0 = {}, rr1 = {};  // the results of steps 0 / 1
     static_for<0, D>([&](auto dd) {
       constexpr int d = decltype(dd)::value;
-      const uint32_t qo = kRotI ? 16u * (uint32_t)((d + lane) & 1) : 0u;  // kRotI: this lane's quad at step d
+      const uint32_t qo = 16u * (uint32_t)((d + lane) & 1);  // this lane's quad at step d
       auto load = [&](auto hh) {
         constexpr int iy = decltype(hh)::value;
 #pragma unroll
         for (int ix = 0; ix < SR; ++ix)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[iy][ix * 4 + q] = lds_read_b128<kRotI ? 0 : 16 * d>(tap(iy, ix, q) + qo);
+          for (int q = 0; q < 4; ++q) v[iy][ix * 4 + q] = lds_read_b128<0>(tap(iy, ix, q) + qo);
       };
       load(std::integral_constant<int, 0>{});
       load(std::integral_constant<int, 1>{});
@@ -1130,30 +1059,19 @@ __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, c
         acc = acc + quad_val(w, &v[1][ix * 4]);
       }
       const f32x4 r4 = acc * 0.25f;  // count 4: / 4 == * 0.25
-      if constexpr (kRotI) {
-        if constexpr (d == 0) rr0 = r4;
-        else rr1 = r4;
-      } else {
-        const int Q = D * s + d;
-        const int vo = Q < nquads ? ovoff : 0x40000000;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.x), orr, vo, (4 * Q) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.y), orr, vo, (4 * Q + 1) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.z), orr, vo, (4 * Q + 2) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.w), orr, vo, (4 * Q + 3) * ostep, kStAux);
-      }
+      if constexpr (d == 0) rr0 = r4;
+      else rr1 = r4;
     });
-    if constexpr (kRotI) {  // quad q of the stage was computed at step (q - lane) & 1
-      const bool sw = (lane & 1) != 0;  // odd lanes: step 0 read quad 1
+    const bool sw = (lane & 1) != 0;  // odd lanes: step 0 read quad 1
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const f32x4 r4 = (q == 0) != sw ? rr0 : rr1;
-        const int Q = 2 * s + q;
-        const int vo = Q < nquads ? ovoff : 0x40000000;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.x), orr, vo, (4 * Q) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.y), orr, vo, (4 * Q + 1) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.z), orr, vo, (4 * Q + 2) * ostep, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.w), orr, vo, (4 * Q + 3) * ostep, kStAux);
-      }
+    for (int q = 0; q < 2; ++q) {  // quad q of the stage was computed at step (q - lane) & 1
+      const f32x4 r4 = (q == 0) != sw ? rr0 : rr1;
+      const int Q = 2 * s + q;
+      const int vo = Q < nquads ? ovoff : 0x40000000;
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.x), orr, vo, (4 * Q) * ostep, kStAux);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.y), orr, vo, (4 * Q + 1) * ostep, kStAux);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.z), orr, vo, (4 * Q + 2) * ostep, kStAux);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.w), orr, vo, (4 * Q + 3) * ostep, kStAux);
     }
     // this stage's tap reads are complete (lds_wait4<0>) before the next stage's DMA
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1171,54 +1089,36 @@ __device__ __forceinline__ void ilv_body(const PairGeom& G, const PairLane& P, c
   }
 }
 
-// kHybrid = D > 0: windows that the quad kernel stages D quads at a time (at most
-// QuadLayout<D, kSlabCells * 16>::kCells cells: every random-init RoI of the bench but a few,
-// most small RoIs) take its path instead -- lane = cell, 64 cells and one address per DMA
-// instruction: fewer instructions where the window is small and the L2 request rate is not
-// the bound -- the rest the bands.
 // band_body: one item (RoI k, 16 channels from chunk) after its RoI setup (G, P of
-// pair_setup<16> when kHybrid or kIlv, else pair_setup<64>); P by value: the band path rescales it.
-template <int kStAux, bool kStamp, int kSlabCells, int kRot = 1, int kHybrid = 0, int kHybridHi = 0,
-          int kIlv = 0, int kOpt = 0>
+// pair_setup<16>); P by value: the band path rescales it.  By the window's cells:
+//  * windows that the quad kernel stages 4 quads at a time (at most QuadLayout<4, kSlabCells *
+//    16>::kCells cells: every random-init RoI of the bench but a few, most small RoIs) take its
+//    path (quad_body) -- lane = cell, 64 cells and one address per DMA instruction: fewer
+//    instructions where the window is small and the L2 request rate is not the bound;
+//  * up to 2 * kSlabCells cells: two whole-window stages of [cell][2 quads] (ilv_body);
+//  * the rest the bands.
+// Measured and rejected: bands only (voc 81-90 us); the quad path's D = 2 / 1
+// stages for windows above 464 / 348 / 696 cells (+-1 us).
+template <bool kStamp, int kSlabCells>
 __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ out, int64_t k, int chunk,
                                           int64_t item, uint32_t sbase, int64_t t_start, int lane, const PairGeom& G,
                                           PairLane P) {
-  constexpr int SR = 2;
+  constexpr int SR = 2, kStAux = kCpolNT;
   int64_t t_setup = 0, t_land = 0;
-  if constexpr (kHybrid > 0 || kIlv > 0) {
-    if constexpr (kHybrid > 0) {
-      if (!G.empty && G.R * G.Cs2 <= QuadLayout<kHybrid, kSlabCells * 16>::kCells) {
-        quad_body<kStAux, kStamp, kQuadWave, 0, kSlabCells * 16, kHybrid == 4, kOpt>(G, P, c, out, k, chunk, item,
-                                                                                    sbase, t_start, lane, nullptr);
-        return;
-      }
-    }
-    if constexpr ((kIlv & 1) != 0) {  // up to kSlabCells cells: one whole-window stage of [cell][4 quads]
-      if (!G.empty && G.R * G.Cs2 <= kSlabCells) {
-        ilv_body<kStAux, kSlabCells, 4, kStamp, kOpt>(G, P, c, out, k, chunk, sbase, lane, item, t_start);
-        return;
-      }
-    }
-    if constexpr ((kIlv & 2) != 0) {  // up to 2 * kSlabCells cells: two whole-window stages of [cell][2 quads]
-      if (!G.empty && G.R * G.Cs2 <= 2 * kSlabCells) {
-        ilv_body<kStAux, kSlabCells, 2, kStamp, kOpt>(G, P, c, out, k, chunk, sbase, lane, item, t_start);
-        return;
-      }
-    }
-    if constexpr (kHybridHi > 0) {  // windows of many bands: the quad kernel's D = 2 / 1 stages instead
-      if (!G.empty && G.R * G.Cs2 > kHybridHi) {
-        quad_body<kStAux, kStamp, kQuadWave, 0, kSlabCells * 16, false, kOpt>(G, P, c, out, k, chunk, item, sbase,
-                                                                             t_start, lane, nullptr);
-        return;
-      }
-    }
+  if (!G.empty && G.R * G.Cs2 <= QuadLayout<4, kSlabCells * 16>::kCells) {
+    quad_body<kStamp, kSlabCells * 16, true, true>(G, P, c, out, k, chunk, item, sbase, t_start, lane);
+    return;
+  }
+  if (!G.empty && G.R * G.Cs2 <= 2 * kSlabCells) {
+    ilv_body<kStamp>(G, P, c, out, k, chunk, sbase, lane, item, t_start);
+    return;
+  }
 #pragma unroll
-    for (int i = 0; i < SR; ++i) {  // the band layout's 64-B cells
-      P.tdq[i] <<= 2;
-      P.tdr[i] <<= 2;
+  for (int i = 0; i < SR; ++i) {  // the band layout's 64-B cells
+    P.tdq[i] <<= 2;
+    P.tdr[i] <<= 2;
 #pragma unroll
-      for (int j = 0; j < SR; ++j) P.tb0[i][j] <<= 2;
-    }
+    for (int j = 0; j < SR; ++j) P.tb0[i][j] <<= 2;
   }
   const int cw0 = chunk * 4 * kQuadWave;
   const int nquads = min(kQuadWave, (c.C - cw0) / 4);  // host: C % 4 == 0
@@ -1242,7 +1142,7 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
   const int soff = cw0 * 4;
   bool pending = active;
   int nbands = 0;
-  f32x4 res0 = {}, res1 = {}, res2 = {}, res3 = {};  // kRot 1 / 3: the step results (named: no indexed array)
+  f32x4 res0 = {}, res1 = {}, res2 = {}, res3 = {};  // the step results (named: no indexed array)
   while (true) {
     const uint64_t pend = __ballot(pending);
     if (!pend) break;
@@ -1263,8 +1163,7 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
       const int r = (int)(((uint32_t)e * inv) >> 16), col = min(e - r * Cs2, Cs - 1);
       const int goff = dense ? ((y0 + rs + r) * sy + (x0 + col) * sx) * 4
                              : __shfl(P.rsrc, rs + r, kWave) + __shfl(P.csrc, col, kWave);
-      lds_dma_at<16, 0>(fr, sbase + 1024u * (uint32_t)j, ((kOpt & kFwdTrim) && !inb) ? 0x40000000 : goff + dq * 16,
-                        soff);
+      lds_dma_at<16, 0>(fr, sbase + 1024u * (uint32_t)j, inb ? goff + dq * 16 : 0x40000000, soff);  // past the band: no load
     }
     wait_vmcnt<0>();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1286,8 +1185,7 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
       }
       static_for<0, kQuadWave>([&](auto dd) {
         constexpr int d = decltype(dd)::value;
-        const int qq = kRot == 1 || kRot == 2 ? (d + lane) & 3 : d;  // this lane's quad at step d
-        const uint32_t qo = 16u * (uint32_t)qq;
+        const uint32_t qo = 16u * (uint32_t)d;  // quad d at step d
         uint32_t lq[SR][SR];
 #pragma unroll
         for (int iy = 0; iy < SR; ++iy)
@@ -1319,34 +1217,11 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
           acc = acc + quad_val(w, &v[1][ix * 4]);
         }
         const f32x4 r4 = acc * 0.25f;  // count 4: / 4 == * 0.25
-        if constexpr (kRot == 1 || kRot == 3) {
-          if constexpr (d == 0) res0 = r4;
-          if constexpr (d == 1) res1 = r4;
-          if constexpr (d == 2) res2 = r4;
-          if constexpr (d == 3) res3 = r4;
-        } else {
-          const int vo = qq < nquads ? lane * 4 + 4 * qq * ostep : 0x40000000;
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.x), orr, vo, 0, kStAux);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.y), orr, vo, ostep, kStAux);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.z), orr, vo, 2 * ostep, kStAux);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r4.w), orr, vo, 3 * ostep, kStAux);
-        }
+        if constexpr (d == 0) res0 = r4;
+        if constexpr (d == 1) res1 = r4;
+        if constexpr (d == 2) res2 = r4;
+        if constexpr (d == 3) res3 = r4;
       });
-      if constexpr (kRot == 1) {  // quad Q was computed at step (Q - lane) mod 4: one channel plane per store
-#pragma unroll
-        for (int Q = 0; Q < kQuadWave; ++Q) {
-          const int sel = (Q - lane) & 3;
-          const bool s0 = sel == 0, s1 = sel == 1, s2 = sel == 2;
-          const float o[4] = {s0 ? res0.x : s1 ? res1.x : s2 ? res2.x : res3.x,
-                              s0 ? res0.y : s1 ? res1.y : s2 ? res2.y : res3.y,
-                              s0 ? res0.z : s1 ? res1.z : s2 ? res2.z : res3.z,
-                              s0 ? res0.w : s1 ? res1.w : s2 ? res2.w : res3.w};
-          const int vo = Q < nquads ? lane * 4 : 0x40000000;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[e]), orr, vo, (4 * Q + e) * ostep, kStAux);
-        }
-      }
       pending = false;
     }
     ++nbands;
@@ -1355,7 +1230,7 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  if constexpr (kRot == 3) {  // every bin's 16 channels after the last band: whole channel rows per store
+  {  // every bin's 16 channels after the last band: whole channel rows per store
     const int vo = active ? lane * 4 : 0x40000000;
     static_for<0, kQuadWave>([&](auto qd) {
       constexpr int Q = decltype(qd)::value;
@@ -1380,27 +1255,25 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
   }
 }
 
-template <int kStAux, bool kStamp, int kSlabCells, int kRot = 1, int kHybrid = 0, int kHybridHi = 0,
-          int kIlv = 0, int kOpt = 0>
+template <bool kStamp, int kSlabCells>
 __device__ __forceinline__ void band_item(const RoiLevels& lv, const RoiCfg& c, float* __restrict__ out, int64_t k,
                                           int chunk, int64_t item, uint32_t sbase, int64_t t_start, int lane) {
   PairGeom G;
   PairLane P;
-  int64_t ko = k;
-  const RoiRaw raw = (kOpt & kFwdSorted) ? roi_fetch_rec(c, k, &ko) : roi_fetch(c, k);
-  pair_setup<(kHybrid || kIlv) ? 16 : 64>(lv, c, raw, lane, G, P);
-  band_body<kStAux, kStamp, kSlabCells, kRot, kHybrid, kHybridHi, kIlv, kOpt>(c, out, ko, chunk, item, sbase, t_start,
-                                                                              lane, G, P);
+  const RoiRaw raw = roi_fetch(c, k);
+  pair_setup<16>(lv, c, raw, lane, G, P);
+  band_body<kStamp, kSlabCells>(c, out, k, chunk, item, sbase, t_start, lane, G, P);
 }
 
 // 1-D grid of 8 * ceil(K * chunks / 8) single-wave workgroups; XCD x takes the x-th eighth of
-// the item list in chunk-pair-major order (quad kernel, kOrder 1: the two 16-channel chunks of
-// a 128-B line, adjacent, on one XCD).
-// kChunks 2: one wave per (RoI, chunk pair) -- both 16-channel chunks of a 128-B line, one after
-// the other on the SAME RoI fetch and setup (the record's first load and pair_setup were ~half of a
-// small item's life); the grid is then 8 * ceil(K * ceil(chunks / 2) / 8).
-template <int kStAux = kCpolNT, bool kStamp = false, int kSlabCells = 208, bool kSpan = false, int kWpe = 3,
-          int kRot = 1, int kHybrid = 0, int kHybridHi = 0, int kIlv = 0, int kChunks = 1, int kOrder = 1, int kOpt = 0>
+// the item list in chunk-pair-major order: the pair's two chunks of a RoI adjacent, (2p, k),
+// (2p + 1, k) -- the two waves reading the two halves of the same 128-B lines run together on
+// one XCD, so the second finds them in L2.
+// Measured and rejected: chunk-major order (bench 43.5 / voc 75.5 / train 69.5 us
+// vs 41.4 / 72.7 / 61.7); one wave per (RoI, chunk pair) on one RoI fetch and setup (47.5 / 79.6 /
+// 71.9 vs 41.2 / 73.0 / 62.2: half as many waves in flight hide less latency than the fetches
+// saved).
+template <int kSlabCells, bool kSpan = false, bool kStamp = false, int kWpe = 3>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kWpe)))
 roi_align_fwd_band_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
   const int64_t t_start = (kStamp || kSpan) ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
@@ -1412,33 +1285,6 @@ roi_align_fwd_band_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
   const uint32_t sbase = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)slab);
   const uint32_t G = (uint32_t)(c.C + kQuadChunk - 1) / (uint32_t)kQuadChunk, K32 = (uint32_t)c.K;
   const int lane = threadIdx.x & (kWave - 1);
-  if constexpr (kChunks == 2) {
-    const uint32_t NP = (G + 1u) / 2u, total = K32 * NP, per = (total + 7u) / 8u;
-    const uint32_t w = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    const uint32_t wend = min((blockIdx.x & 7u) * per + per, total);
-    if (w >= wend) return;
-    const uint32_t p = w / K32, k = w - p * K32;
-    PairGeom Gm;
-    PairLane P;
-    const RoiRaw raw = roi_fetch(c, (int64_t)k);
-    pair_setup<(kHybrid || kIlv) ? 16 : 64>(lv, c, raw, lane, Gm, P);
-    const bool two = 2u * p + 1u < G;
-    const int64_t item0 = (int64_t)p * 2 * K32 + (two ? 2 * k : k);
-    band_body<kStAux, kStamp, kSlabCells, kRot, kHybrid, kHybridHi, kIlv, kOpt>(c, out, (int64_t)k, (int)(2u * p),
-                                                                                item0, sbase, t_start, lane, Gm, P);
-    if (two) {
-      // the first chunk's tap reads are complete (its evaluation waited on them) before the
-      // second chunk's DMA overwrites the slab
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      band_body<kStAux, kStamp, kSlabCells, kRot, kHybrid, kHybridHi, kIlv, kOpt>(c, out, (int64_t)k,
-                                                                                  (int)(2u * p + 1u), item0 + 1, sbase,
-                                                                                  t_start, lane, Gm, P);
-    }
-    if (kSpan && threadIdx.x == 0) record_span(c, t_start);
-    return;
-  }
   const uint32_t total = K32 * G, per = (total + 7u) / 8u;
   const uint32_t w = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
   const uint32_t wend = min((blockIdx.x & 7u) * per + per, total);
@@ -1446,18 +1292,14 @@ roi_align_fwd_band_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
   const uint32_t p = w / (2u * K32), r = w - p * 2u * K32;
   int ch0;
   int64_t k0;
-  if (kOrder == 0) {  // chunk-major: XCD x walks its eighth of the (chunk, RoI) list
-    ch0 = (int)(w / K32);
-    k0 = (int64_t)(w - (uint32_t)ch0 * K32);
-  } else if (2u * p + 1u < G) {
+  if (2u * p + 1u < G) {
     ch0 = (int)(2u * p + (r & 1u));
     k0 = (int64_t)(r >> 1);
   } else {  // odd chunk count: the last chunk alone
     ch0 = (int)(2u * p);
     k0 = (int64_t)r;
   }
-  band_item<kStAux, kStamp, kSlabCells, kRot, kHybrid, kHybridHi, kIlv, kOpt>(lv, c, out, k0, ch0, w, sbase, t_start,
-                                                                              lane);
+  band_item<kStamp, kSlabCells>(lv, c, out, k0, ch0, w, sbase, t_start, lane);
   if (kSpan && threadIdx.x == 0) record_span(c, t_start);
 }
 
@@ -1488,18 +1330,18 @@ constexpr bool band_fits(int ph, int pw, int slab_cells) { return 5 * ((4 * pw) 
 // order, then / 4): bit-identical.
 constexpr int kCgChan = 64;  // channels per item
 
-// kLd2: both sample rows' 16 tap reads in flight together (else the second row's 8 after the
-// first row's sums: 32 VGPRs fewer)
-// kOrder 0: XCD x walks the x-th eighth of the group-major (group, RoI) list (each XCD's L2 holds
-// one 64-channel slice); 1: RoI-major (RoI, group) -- the 4 groups of a RoI adjacent.
+// One sample row's 8 tap reads are in flight at a time: the second row's are issued after the
+// first row's sums (32 VGPRs fewer than both rows' 16 in flight, which measured 2-6 % slower at
+// 4 workgroups per CU and spilled when forced to 5: DESIGN.md §4).  XCD x walks the x-th eighth
+// of the group-major (group, RoI) list (each XCD's L2 holds one 64-channel slice; RoI-major order
+// measured 14 % slower on the bench set).  kWpe 0: the compiler's choice of waves per SIMD.
 // kStamp (tools-only timing builds): thread 0 writes 16 int64 per item after the output --
 // s_memrealtime at start / setup done / first band landed / end, bands, window cells, RoI record
 // landed, evaluation done, taps made, window extents, tables written.
-template <int kNW, int kSlabCells, int kStAux = kCpolNT, bool kSpan = false, int kWpe = 0, bool kLd2 = true,
-          int kOrder = 0, bool kStamp = false>
+template <int kNW, int kSlabCells, bool kSpan = false, int kWpe = 0, bool kStamp = false>
 __global__ void __launch_bounds__(kNW * kWave) __attribute__((amdgpu_waves_per_eu(kWpe > 0 ? kWpe : 1)))
 roi_align_fwd_cg_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
-  constexpr int SR = 2;
+  constexpr int SR = 2, kStAux = kCpolNT;
   constexpr int kJ = 16 / kNW;  // 4-bin steps per wave (<= 64 bins)
   static_assert(kNW == 2 || kNW == 4 || kNW == 8, "waves per workgroup");
   static_assert(kSlabCells >= 64 && kSlabCells % 4 == 0, "the output block [64][<= 64 bins] leaves through the slab");
@@ -1518,8 +1360,8 @@ roi_align_fwd_cg_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
   const uint32_t total = K32 * NG, per = (total + 7u) / 8u;
   const uint32_t w = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
   if (w >= min((blockIdx.x & 7u) * per + per, total)) return;
-  const uint32_t grp = kOrder == 0 ? w / K32 : w % NG;
-  const int64_t k = kOrder == 0 ? (int64_t)(w - grp * K32) : (int64_t)(w / NG);
+  const uint32_t grp = w / K32;
+  const int64_t k = (int64_t)(w - grp * K32);
   const int nbins = c.ph * c.pw;
   const int nq = nbins * kCgChan / 4;  // 16-B units of the item's output block
   const __amdgpu_buffer_rsrc_t orr = uniform_rsrc(out + (k * c.C + (int64_t)grp * kCgChan) * nbins, (int64_t)nq * 16);
@@ -1692,19 +1534,15 @@ roi_align_fwd_cg_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
         }
       };
       load(std::integral_constant<int, 0>{});
-      if constexpr (kLd2) load(std::integral_constant<int, 1>{});
       f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (kLd2) lds_wait4<8>(v[0]);
-      else lds_wait4<0>(v[0]);
+      lds_wait4<0>(v[0]);
 #pragma unroll
       for (int ix = 0; ix < SR; ++ix) {
         const float wq[4] = {Y[0].w * X[ix].w, Y[0].w * X[ix].z, Y[0].z * X[ix].w, Y[0].z * X[ix].z};
         acc = acc + quad_val(wq, &v[0][ix * 4]);
       }
-      if constexpr (!kLd2) {
-        asm volatile("" : "+v"(acc));  // the first row's sums before the second row's reads: v[0] dies here
-        load(std::integral_constant<int, 1>{});
-      }
+      asm volatile("" : "+v"(acc));  // the first row's sums before the second row's reads: v[0] dies here
+      load(std::integral_constant<int, 1>{});
       lds_wait4<0>(v[1]);
 #pragma unroll
       for (int ix = 0; ix < SR; ++ix) {
@@ -1752,295 +1590,6 @@ roi_align_fwd_cg_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
     st[9] = t_ext;
     st[10] = t_tab;
   }
-}
-
-// ---------------------------------------------------------------------------
-// The channel-group forward with kItems items per workgroup, software-pipelined (round 6): the
-// next item's RoI record, window and sample tables (the ~1.5-2 us setup chain: scalar loads, tap
-// math, tables) are computed while the current item's window DMA is in flight, and the slab is
-// never idle during a setup.  Tables double-buffered; barriers wait for LDS only (the output
-// stores drain in the background).  Item j of workgroup r of XCD x: x * per + r + j * nwx (per
-// items per XCD, nwx workgroups per XCD), so the resident workgroups of an XCD stay on nearby
-// RoIs of one channel group.  Same evaluation as roi_align_fwd_cg_kernel: bit-identical.
-__device__ __forceinline__ void lds_only_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-struct CgItem {  // wave-uniform (SGPRs); the per-lane tables live in LDS (CgTab)
-  const float* base;  // image b of the RoI's level
-  uint32_t extent;    // feature bytes addressable from base
-  int k, grp, state;  // state 0: none, 1: no valid sample (zeros), 2: staged and evaluated
-  int R, Cs, dy, multi, rows_cap;
-  float rcs;
-};
-
-// An item's LDS tables (written by wave 0 in cg_setup): the sample tables (y samples [0, 16), x
-// [16, 32): slab row / column of the lo tap, hi - lo, l, h), the source byte offsets of the window
-// rows (dense or tap-list) and columns, the tap-list rows (list bands), bin-row row spans.
-struct CgTab {
-  float4 smp[32];
-  int rsrc[32], rsrcl[32], csrc[32];
-  int brl[8], brh[8];
-};
-
-template <int kSlabCells>
-__device__ __forceinline__ void cg_setup(const RoiLevels& lv, const RoiCfg& c, uint32_t w, uint32_t wend, CgTab* tb,
-                                         int lane, int wave, CgItem& it) {
-  constexpr int SR = 2;
-  if (w >= wend) {
-    it.state = 0;
-    return;
-  }
-  const uint32_t K32 = (uint32_t)c.K;
-  it.grp = (int)(w / K32);
-  it.k = (int)(w - (uint32_t)it.grp * K32);
-  const RoiRaw raw = roi_fetch(c, (int64_t)it.k);
-  const RoiGeom g = roi_geom_raw(c, lv, raw);
-  const int l = g.lvl;
-  const int H = lv.h[l], W = lv.w[l];
-  const int sy = (int)lv.sy[l], sx = (int)lv.sx[l];
-  const bool isx = lane >= 32;
-  const int e = lane & 31;
-  const int nl = isx ? 2 * SR * c.pw : 2 * SR * c.ph;
-  int trow = -1, tlo = 0x7fffffff, thi = -1;
-  float tl = 0.f, th = 0.f;
-  if (e < nl) {
-    const int s = e >> 1, p = s >> 1, i = s & 1;
-    const float v = isx ? g.start_w + (float)p * g.bin_w + ((float)i + 0.5f) * g.bin_w * 0.5f
-                        : g.start_h + (float)p * g.bin_h + ((float)i + 0.5f) * g.bin_h * 0.5f;
-    const Tap t = make_tap(v, isx ? W : H);
-    if (t.valid) trow = (e & 1) ? t.hi : t.lo, tlo = t.lo, thi = t.hi, tl = t.l, th = t.h;
-  }
-  const uint64_t vm = __ballot(trow >= 0);
-  const uint32_t vy = (uint32_t)vm, vx = (uint32_t)(vm >> 32);
-  if (!vy || !vx) {
-    it.state = 1;
-    return;
-  }
-  it.state = 2;
-  const int y0 = __builtin_amdgcn_readlane(tlo, __builtin_ctz(vy));
-  const int y1 = __builtin_amdgcn_readlane(thi, 31 - __builtin_clz(vy));
-  const int x0 = __builtin_amdgcn_readlane(tlo, 32 + __builtin_ctz(vx));
-  const int x1 = __builtin_amdgcn_readlane(thi, 63 - __builtin_clz(vx));
-  const int nly = 2 * SR * c.ph, nlx = 2 * SR * c.pw;
-  const bool dy = y1 - y0 + 1 <= nly, dx = x1 - x0 + 1 <= nlx;
-  it.dy = dy;
-  it.R = dy ? y1 - y0 + 1 : nly;
-  it.Cs = dx ? x1 - x0 + 1 : nlx;
-  it.multi = it.R * it.Cs > kSlabCells;
-  it.rcs = __builtin_amdgcn_rcpf((float)it.Cs);
-  it.rows_cap = it.multi ? (int)(((float)kSlabCells + 0.5f) * it.rcs) : kSlabCells;
-  it.base = lv.feat[l] + (int64_t)g.b * lv.sb[l];
-  it.extent = (uint32_t)(((int64_t)(c.C - 1) + (int64_t)(H - 1) * sy + (int64_t)(W - 1) * sx + 1) * 4);
-  if (wave == 0) {
-    const bool dax = isx ? dx : dy;
-    const int org = isx ? x0 : y0;
-    const int src = (dax ? org + min(e, (isx ? it.Cs : it.R) - 1) : (trow >= 0 ? trow : org)) * (isx ? sx : sy) * 4;
-    if (isx) {
-      tb->csrc[e] = src;
-    } else {
-      tb->rsrc[e] = src;
-      tb->rsrcl[e] = (trow >= 0 ? trow : org) * sy * 4;
-    }
-    const bool tv = e < nl && trow >= 0 && (e & 1) == 0;
-    const int r0 = tv ? (dax ? tlo - org : e) : 0, dr = tv ? (dax ? thi - tlo : 1) : 0;
-    if ((e & 1) == 0)
-      tb->smp[(isx ? 16 : 0) + (e >> 1)] = float4{__int_as_float(r0), __int_as_float(dr), tv ? tl : 0.f, tv ? th : 0.f};
-    if (it.multi) {
-      const int rl = tv ? r0 : 0x7fffffff, rh = tv ? r0 + dr : -1;
-      const int pr = min(lane, 15);
-      const int a = min(__shfl(rl, 4 * pr, kWave), __shfl(rl, 4 * pr + 2, kWave));
-      const int b = max(__shfl(rh, 4 * pr, kWave), __shfl(rh, 4 * pr + 2, kWave));
-      if (lane < 8) tb->brl[lane] = a, tb->brh[lane] = b;
-    }
-  }
-}
-
-// one item: its bands (staging, evaluation), the output block; hook() runs once, right after
-// the first band's DMA is issued (or at once for an item without a valid sample)
-template <int kNW, int kSlabCells, int kStAux, bool kLd2, typename Hook>
-__device__ __forceinline__ void cg_body(const RoiCfg& c, const CgItem& it, float* __restrict__ out, float* slab,
-                                        uint32_t sbase, const CgTab* tb, int lane, int wave, Hook&& hook) {
-  const uint32_t tbase = (uint32_t)reinterpret_cast<uintptr_t>(
-      (__attribute__((address_space(3))) const float4*)reinterpret_cast<const float4*>(tb->smp));
-  constexpr int SR = 2;
-  constexpr int kJ = 16 / kNW;
-  const int nbins = c.ph * c.pw;
-  const int nq = nbins * kCgChan / 4;
-  if (it.state == 1) {
-    const __amdgpu_buffer_rsrc_t orr =
-        uniform_rsrc(out + ((int64_t)it.k * c.C + (int64_t)it.grp * kCgChan) * nbins, (int64_t)nq * 16);
-    for (int u = (int)threadIdx.x; u < nq; u += kNW * kWave)
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, orr, u * 16, 0, kStAux);
-    hook();
-    return;
-  }
-  const int R = it.R, Cs = it.Cs;
-  const float rcs = it.rcs;
-  const int soff = it.grp * kCgChan * 4;
-  const int q = lane & 15, b4 = lane >> 4;
-  f32x4 res[kJ];
-#pragma unroll
-  for (int j = 0; j < kJ; ++j) res[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int pb = 0;
-  bool first = true;
-  while (pb < c.ph) {
-    int rs = 0x7fffffff, re = -1, pe = pb;
-    if (!it.multi) {
-      rs = 0, re = R - 1, pe = c.ph;
-    } else {
-      while (pe < c.ph) {
-        const int lo = __builtin_amdgcn_readfirstlane(tb->brl[pe]), hi = __builtin_amdgcn_readfirstlane(tb->brh[pe]);
-        if (hi >= 0) {
-          const int nrs = min(rs, lo), nre = max(re, hi);
-          if (pe > pb && nre - nrs + 1 > it.rows_cap) break;
-          rs = nrs, re = nre;
-        }
-        ++pe;
-      }
-      if (re < 0) rs = re = 0;
-    }
-    const bool lst = it.multi && it.dy && re - rs + 1 > it.rows_cap;
-    if (lst) rs = 4 * pb, re = 4 * pb + 3, pe = pb + 1;
-    const int nb = (re - rs + 1) * Cs;
-    const int nj = (nb + 3) >> 2;
-    for (int J = wave; J < nj; J += kNW) {
-      int cell = 4 * J + b4;
-      const bool in = cell < nb;
-      cell = in ? cell : 0;
-      const int r = (int)(((float)cell + 0.5f) * rcs), cc = cell - r * Cs;
-      const int voff = (lst ? tb->rsrcl[rs + r] : tb->rsrc[rs + r]) + tb->csrc[cc] + q * 16;
-      lds_dma_at<16, 0>(uniform_rsrc(it.base, (int64_t)it.extent), sbase + 1024u * (uint32_t)J,
-                        in ? voff : 0x40000000, soff);
-    }
-    if (first) {
-      hook();  // the next item's setup while this DMA is in flight
-      first = false;
-    }
-    wait_vmcnt<0>();
-    lds_only_barrier();  // every wave's DMA (and the tables) landed
-    const int bin_lo = pb * c.pw, bin_hi = min(pe * c.pw, nbins);
-    const int rsb = rs;
-#pragma unroll
-    for (int j = 0; j < kJ; ++j) {
-      const int t = wave + kNW * j;
-      if (4 * t + 3 < bin_lo || 4 * t >= bin_hi) continue;
-      int b4o = b4;
-      asm volatile("" : "+v"(b4o));
-      const int bin = 4 * t + b4o;
-      const bool act = bin >= bin_lo && bin < bin_hi;
-      const int bq = act ? bin : bin_lo;
-      const int py = (int)(((uint32_t)bq * ((65536u + (uint32_t)c.pw - 1u) / (uint32_t)c.pw)) >> 16), px = bq - py * c.pw;
-      f32x4 Y[2], X[2];
-      Y[0] = lds_read_b128<0>(tbase + 32u * (uint32_t)py);
-      Y[1] = lds_read_b128<16>(tbase + 32u * (uint32_t)py);
-      X[0] = lds_read_b128<256>(tbase + 32u * (uint32_t)px);
-      X[1] = lds_read_b128<272>(tbase + 32u * (uint32_t)px);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Y[0]), "+v"(Y[1]), "+v"(X[0]), "+v"(X[1]) : : "memory");
-      uint32_t ra[SR], rd[SR], ca[SR], cd[SR];
-#pragma unroll
-      for (int i = 0; i < SR; ++i) {
-        const int ry = lst ? 4 * py + 2 * i - rsb : max(__float_as_int(Y[i].x) - rsb, 0);
-        ra[i] = (uint32_t)(ry * Cs) * 256u;
-        rd[i] = (uint32_t)((lst ? 1 : __float_as_int(Y[i].y)) * Cs) * 256u;
-        ca[i] = (uint32_t)__float_as_int(X[i].x) * 256u;
-        cd[i] = (uint32_t)__float_as_int(X[i].y) * 256u;
-      }
-      const uint32_t qb = sbase + 16u * (uint32_t)q;
-      f32x4 v[2][8];
-      auto load = [&](auto hh) {
-        constexpr int iy = decltype(hh)::value;
-#pragma unroll
-        for (int ix = 0; ix < SR; ++ix) {
-          const uint32_t a = qb + ra[iy] + ca[ix];
-          v[iy][ix * 4 + 0] = lds_read_b128<0>(a);
-          v[iy][ix * 4 + 1] = lds_read_b128<0>(a + cd[ix]);
-          v[iy][ix * 4 + 2] = lds_read_b128<0>(a + rd[iy]);
-          v[iy][ix * 4 + 3] = lds_read_b128<0>(a + rd[iy] + cd[ix]);
-        }
-      };
-      load(std::integral_constant<int, 0>{});
-      if constexpr (kLd2) load(std::integral_constant<int, 1>{});
-      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (kLd2) lds_wait4<8>(v[0]);
-      else lds_wait4<0>(v[0]);
-#pragma unroll
-      for (int ix = 0; ix < SR; ++ix) {
-        const float wq[4] = {Y[0].w * X[ix].w, Y[0].w * X[ix].z, Y[0].z * X[ix].w, Y[0].z * X[ix].z};
-        acc = acc + quad_val(wq, &v[0][ix * 4]);
-      }
-      if constexpr (!kLd2) {
-        asm volatile("" : "+v"(acc));
-        load(std::integral_constant<int, 1>{});
-      }
-      lds_wait4<0>(v[1]);
-#pragma unroll
-      for (int ix = 0; ix < SR; ++ix) {
-        const float wq[4] = {Y[1].w * X[ix].w, Y[1].w * X[ix].z, Y[1].z * X[ix].w, Y[1].z * X[ix].z};
-        acc = acc + quad_val(wq, &v[1][ix * 4]);
-      }
-      if (act) res[j] = acc * 0.25f;
-    }
-    lds_only_barrier();  // the band's tap reads are done before the next band (or the outputs) overwrite the slab
-    pb = pe;
-  }
-  float* ob = slab;
-#pragma unroll
-  for (int j = 0; j < kJ; ++j) {
-    const int bin = 4 * (wave + kNW * j) + b4;
-    if (bin < nbins) {
-      ob[(4 * q + 0) * nbins + bin] = res[j].x;
-      ob[(4 * q + 1) * nbins + bin] = res[j].y;
-      ob[(4 * q + 2) * nbins + bin] = res[j].z;
-      ob[(4 * q + 3) * nbins + bin] = res[j].w;
-    }
-  }
-  lds_only_barrier();
-  const __amdgpu_buffer_rsrc_t orr =
-      uniform_rsrc(out + ((int64_t)it.k * c.C + (int64_t)it.grp * kCgChan) * nbins, (int64_t)nq * 16);
-  const float4* o4 = reinterpret_cast<const float4*>(slab);
-  for (int u = (int)threadIdx.x; u < nq; u += kNW * kWave) {
-    const float4 v4 = o4[u];
-    __builtin_amdgcn_raw_buffer_store_b128(
-        u32x4{__float_as_uint(v4.x), __float_as_uint(v4.y), __float_as_uint(v4.z), __float_as_uint(v4.w)}, orr,
-        u * 16, 0, kStAux);
-  }
-  lds_only_barrier();  // the output block's reads are done before the next item's DMA overwrites the slab
-}
-
-template <int kNW, int kSlabCells, int kItems, int kStAux = kCpolNT, bool kSpan = false, int kWpe = 0,
-          bool kLd2 = false>
-__global__ void __launch_bounds__(kNW * kWave) __attribute__((amdgpu_waves_per_eu(kWpe > 0 ? kWpe : 1)))
-roi_align_fwd_cgp_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
-  static_assert(kNW == 2 || kNW == 4 || kNW == 8, "waves per workgroup");
-  static_assert(kSlabCells >= 64 && kSlabCells % 4 == 0, "the output block [64][<= 64 bins] leaves through the slab");
-  static_assert((kSlabCells + 3) / 4 <= 63 * kNW, "vmcnt is 6 bits");
-  const int64_t t_start = kSpan ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
-  __shared__ __attribute__((aligned(16))) float slab[kSlabCells * kCgChan];
-  __shared__ CgTab tab[2];  // double-buffered item tables
-  const uint32_t sbase = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)slab);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-  const uint32_t total = (uint32_t)c.K * ((uint32_t)c.C / kCgChan), per = (total + 7u) / 8u;
-  const uint32_t nwx = (per + kItems - 1u) / kItems;  // workgroups per XCD
-  const uint32_t x = blockIdx.x & 7u, r = blockIdx.x >> 3;
-  const uint32_t wend = min(x * per + per, total);
-  uint32_t w = x * per + r;
-  CgItem cur, nxt;
-  cg_setup<kSlabCells>(lv, c, w, wend, &tab[0], lane, wave, cur);
-  lds_only_barrier();  // the first item's tables
-  int b = 0;
-  for (int j = 0; j < kItems && cur.state; ++j) {
-    const uint32_t wn = j + 1 < kItems ? w + nwx : wend;
-    nxt.state = 0;
-    cg_body<kNW, kSlabCells, kStAux, kLd2>(c, cur, out, slab, sbase, &tab[b], lane, wave, [&] {
-      cg_setup<kSlabCells>(lv, c, wn, wend, &tab[b ^ 1], lane, wave, nxt);
-    });
-    cur = nxt;
-    w = wn;
-    b ^= 1;
-  }
-  if (kSpan && threadIdx.x == 0) record_span(c, t_start);
 }
 
 // shapes the channel-group kernel takes: channels-last (quad_ok), C % 64 == 0, sampling 2, tap
@@ -2536,123 +2085,6 @@ __global__ void __launch_bounds__(kNW * kWave) roi_align_bwd_nhwc_kernel(RoiLeve
   }
 }
 
-// The channels-last backward with the tap lists in registers (round 6): the sorted y / x tap
-// entries sit one per lane and are read by v_readlane with the wave-uniform loop index (a
-// scalar, no LDS round trip), the row sums R[px] stay in registers and the column loop picks
-// R[px] by a uniform select -- the round-5 kernel read each x entry, its weight and R[px]
-// from LDS in a dependent chain (two LDS round trips per (row, column) pair: ~50 us of serial
-// latency per wave on VOC-sized windows).  Same sums in the same order: each cell's
-// contribution is bit-identical to roi_align_bwd_nhwc_kernel's.
-// kStore (tools-only diagnostic): plain stores instead of the atomics (wrong sums): the kernel's
-// time without the atomic traffic; kDiag (tools-only): 1 = no column loop (the row sums stored),
-// 2 = return after the tap-entry setup
-template <bool kFixed = false, bool kStore = false, int kDiag = 0>
-__global__ void __launch_bounds__(kWave) roi_align_bwd_nhwc2_kernel(RoiLevels lv, RoiCfg c,
-                                                                  const float* __restrict__ gout) {
-  constexpr int kMaxP = 8;
-  __shared__ __attribute__((aligned(16))) float gs[kMaxP * kMaxP * kWave];  // grad_out, [lane][bin]
-  __shared__ int ye[kSepEnt], xe[kSepEnt];     // sorted tap entries: position << 16 | bin index
-  __shared__ float yws[kSepEnt], xws[kSepEnt];
-  const int64_t k = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int c0 = blockIdx.y * kWave, ch = c0 + lane;
-  const bool live = ch < c.C;
-  const RoiGeom g = roi_geom(c, lv, k);
-  const int l = g.lvl, H = lv.h[l], W = lv.w[l];
-  const int ph = c.ph, pw = c.pw, nbins = ph * pw, nye = 4 * ph, nxe = 4 * pw;
-  {  // the wave's contiguous [64][bins] grad_out block by LDS-DMA (as roi_align_bwd_nhwc_kernel)
-    const float* go = gout + (k * c.C + c0) * nbins;
-    const int nvalid = min(kWave, c.C - c0) * nbins;
-    const __amdgpu_buffer_rsrc_t gr = uniform_rsrc(go, (int64_t)nvalid * 4);
-    const uint32_t gsb = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)gs);
-    for (int i0 = 0; i0 < nbins; i0 += 32) {
-      const int i1 = min(nbins, i0 + 32);
-      for (int i = i0; i < i1; ++i) lds_dma_at<4, 0>(gr, gsb + 256u * (uint32_t)i, lane * 4, i * 256);
-      wait_vmcnt<0>();
-    }
-  }
-  auto entry = [&](int e, float start, float bin, int size, int* pos, float* w) {
-    const Tap t = make_tap(start + (float)(e >> 2) * bin + ((float)((e >> 1) & 1) + 0.5f) * bin * 0.5f, size);
-    *pos = t.valid ? ((e & 1) ? t.hi : t.lo) : -1;
-    *w = (e & 1) ? t.l : t.h;
-  };
-  int yp = -1, xp = -1;
-  float ywv = 0.0f, xwv = 0.0f;
-  if (lane < nye) entry(lane, g.start_h, g.bin_h, H, &yp, &ywv);
-  if (lane < nxe) entry(lane, g.start_w, g.bin_w, W, &xp, &xwv);
-  if (lane >= nye) yp = -1;
-  if (lane >= nxe) xp = -1;
-  const int ypm = yp < 0 ? (1 << 20) : yp, xpm = xp < 0 ? (1 << 20) : xp;
-  int yr = 0, xr = 0;  // rank by (position, entry)
-  for (int e = 0; e < nye; ++e) {
-    const int pe = __shfl(ypm, e, kWave);
-    yr += (pe < ypm || (pe == ypm && e < lane)) ? 1 : 0;
-  }
-  for (int e = 0; e < nxe; ++e) {
-    const int pe = __shfl(xpm, e, kWave);
-    xr += (pe < xpm || (pe == xpm && e < lane)) ? 1 : 0;
-  }
-  if (yp >= 0) ye[yr] = (yp << 16) | (lane >> 2), yws[yr] = ywv;
-  if (xp >= 0) xe[xr] = (xp << 16) | (lane >> 2), xws[xr] = xwv;
-  const int nyv = __popcll(__ballot(yp >= 0)), nxv = __popcll(__ballot(xp >= 0));
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (nyv == 0 || nxv == 0) return;  // no valid tap: no gradient
-  if (kDiag == 2) {
-    if (ye[0] == 0x7fffffff) lv.grad[l][lane] = 1.0f;  // keep the setup alive
-    return;
-  }
-  // lane i holds sorted entry i of each axis (read by v_readlane below)
-  const int ye_l = lane < kSepEnt ? ye[lane] : 0, xe_l = lane < kSepEnt ? xe[lane] : 0;
-  const float yw_l = lane < kSepEnt ? yws[lane] : 0.0f, xw_l = lane < kSepEnt ? xws[lane] : 0.0f;
-  const int64_t base = (int64_t)g.b * lv.sb[l] + ch, sy = lv.sy[l], sx = lv.sx[l];
-  const double fscale = kFixed ? bwd_fixed_scale(c.fix_max, c.fix_hb) : 0.0;
-  if (kFixed && fscale < 0.0) return;  // non-finite gradient: the conversion writes NaN
-  float R[kMaxP];
-#pragma unroll
-  for (int px = 0; px < kMaxP; ++px) R[px] = 0.0f;
-  for (int i = 0; i < nyv; ++i) {
-    const int yv = __builtin_amdgcn_readlane(ye_l, i), row = yv >> 16, py = yv & 0xffff;
-    const float wy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(yw_l), i));
-    const float* gr = gs + lane * nbins + py * pw;
-#pragma unroll
-    for (int px = 0; px < kMaxP; ++px)
-      if (px < pw) R[px] = R[px] + wy * gr[px];
-    if (i + 1 < nyv && (__builtin_amdgcn_readlane(ye_l, i + 1) >> 16) == row) continue;  // the row continues
-    if (kDiag == 1) {
-      float t = 0.0f;
-#pragma unroll
-      for (int px = 0; px < kMaxP; ++px) t = t + R[px], R[px] = 0.0f;
-      if (live) __builtin_nontemporal_store(t, lv.grad[l] + base + (int64_t)row * sy);
-      continue;
-    }
-    float acc = 0.0f;
-    for (int jx = 0; jx < nxv; ++jx) {
-      const int xv = __builtin_amdgcn_readlane(xe_l, jx), col = xv >> 16, px = xv & 0xffff;
-      const float wx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xw_l), jx));
-      float r = R[0];
-#pragma unroll
-      for (int q = 1; q < kMaxP; ++q) r = px == q ? R[q] : r;  // uniform select
-      acc = acc + wx * r;
-      if (jx + 1 < nxv && (__builtin_amdgcn_readlane(xe_l, jx + 1) >> 16) == col) continue;
-      const float v = acc * 0.25f;  // / count (4 samples)
-      acc = 0.0f;
-      if (!live || v == 0.0f) continue;
-      const int64_t e = base + (int64_t)row * sy + (int64_t)col * sx;
-      if constexpr (kStore)
-        __builtin_nontemporal_store(v, lv.grad[l] + e);
-      else if constexpr (kFixed)
-        atomicAdd(reinterpret_cast<unsigned long long*>(lv.grad[l]) + e,
-                  (unsigned long long)(long long)rint((double)v * fscale));
-      else
-        atomicAdd(lv.grad[l] + e, v);
-    }
-#pragma unroll
-    for (int px = 0; px < kMaxP; ++px) R[px] = 0.0f;
-  }
-}
-
 // the fixed-point accumulators to the f32 gradient, element by element (dense buffers)
 static __global__ void roi_bwd_fixed_to_f32_kernel(const long long* __restrict__ acc, float* __restrict__ grad, int64_t n,
                                                    const uint32_t* fix_max, int hb) {
@@ -2660,197 +2092,6 @@ static __global__ void roi_bwd_fixed_to_f32_kernel(const long long* __restrict__
   const double inv = s > 0.0 ? 1.0 / s : (double)NAN;  // 1 / 2^k is exact
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
     grad[q] = (float)((double)acc[q] * inv);
-}
-
-// ---------------------------------------------------------------------------
-// Channels-last forward (features with unit channel stride: the FPN's NHWC outputs).
-// One wave per (RoI, 64 channels), lane = channel: every tap is wave-uniform, so the
-// sample geometry is computed once per wave (14 y- and 14 x-samples, one lane each,
-// broadcast by v_readlane) and every feature access is a 256-B run of one cell's
-// channels.  The RoI's tap cells (the dense window [y0, y1] x [x0, x1], or per axis the
-// 2 * 2 * P (lo, hi) tap list when the window is wider -- as the pair kernel) are staged
-// into the wave's LDS slab by 16-B LDS-DMA, one 1-KB instruction per 4 cells (full
-// 128-B lines); a window with more than kCells cells is staged in bands of slab rows,
-// each band holding whole sample rows.  Each sample's four taps are ds_read_b32 of
-// consecutive channels (conflict-free); the bilinear sums run per lane in torchvision's
-// operation order, so the result is bit-identical to the other kernels.  The 7 x 7
-// outputs of the lane's channel collect in VGPRs and leave through the slab, transposed
-// to [channel][bin], as 16-B stores of one contiguous 12.5-KB block.
-constexpr int kNhwcGroup = 64;  // channels per wave
-
-// kRegOut: the outputs stay in VGPRs until the end (LDS = the slab only) instead of a
-// separate [channel][bin] LDS buffer.  kStamp (tools-only timing builds): lane 0 writes 8
-// int64 per item after the output -- s_memrealtime at start / prologue done / first band
-// landed / eval done / end, bands staged, cells of the first band, XCD.
-template <int PH, int PW, int kCells, int kStAux, bool kRegOut = true, bool kStamp = false>
-__global__ void __launch_bounds__(kWave) roi_align_fwd_nhwc_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
-  const int64_t t_start = kStamp ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
-  int64_t t_pro = 0, t_land = 0, t_eval = 0;
-  int n_bands = 0, first_cells = 0;
-  static_assert(2 * PH <= 32 && 2 * PW <= 32 && kCells % 4 == 0 && kCells >= 2 * 4 * PW, "tap lanes / DMA rounds");
-  static_assert(!kRegOut || kCells >= PH * PW, "the outputs leave through the slab");
-  constexpr int NLY = 4 * PH, NLX = 4 * PW;  // tap-list lengths
-  constexpr int NB = PH * PW;
-  __shared__ __attribute__((aligned(16))) float slab[kCells * kNhwcGroup];
-  __shared__ __attribute__((aligned(16))) float obuf[kRegOut ? 4 : kNhwcGroup * NB];  // [channel][bin]
-  const uint32_t sbase = (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)slab);
-  const int lane = threadIdx.x;
-  // XCD x (= workgroup id mod 8) walks the x-th eighth of the group-major (group, RoI) list
-  const uint32_t G = (uint32_t)c.C / kNhwcGroup, K32 = (uint32_t)c.K;
-  const uint32_t total = K32 * G, per = (total + 7u) / 8u;
-  const uint32_t w = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-  if (w >= min((blockIdx.x & 7u) * per + per, total)) return;
-  const int grp = (int)(w / K32);
-  const int64_t k = (int64_t)(w - (uint32_t)grp * K32);
-  const RoiRaw raw = roi_fetch(c, k);
-  const RoiGeom g = roi_geom_raw(c, lv, raw);
-  const int l = g.lvl, H = lv.h[l], W = lv.w[l];
-  // lane s < 2 PH: y sample s (bin s / 2, sub-sample s % 2); lane 32 + s < 32 + 2 PW: x sample s
-  const bool isy = lane < 2 * PH, isx = lane >= 32 && lane < 32 + 2 * PW;
-  const int s = isy ? lane : lane - 32;
-  Tap t{0, 0, 0.f, 0.f, 0};
-  if (isy || isx) {
-    const float st = isy ? g.start_h : g.start_w, bn = isy ? g.bin_h : g.bin_w;
-    t = make_tap(st + (float)(s >> 1) * bn + ((float)(s & 1) + 0.5f) * bn * 0.5f, isy ? H : W);
-  }
-  const bool tv = (isy || isx) && t.valid;
-  const int y0 = __builtin_amdgcn_readfirstlane(wave_min_i32(isy && tv ? t.lo : 1 << 30));
-  const int y1 = __builtin_amdgcn_readfirstlane(wave_max_i32(isy && tv ? t.hi : -1));
-  const int x0 = __builtin_amdgcn_readfirstlane(wave_min_i32(isx && tv ? t.lo : 1 << 30));
-  const int x1 = __builtin_amdgcn_readfirstlane(wave_max_i32(isx && tv ? t.hi : -1));
-  float* o = out + (k * c.C + (int64_t)grp * kNhwcGroup) * NB;  // [64][NB], contiguous
-  const __amdgpu_buffer_rsrc_t orr = uniform_rsrc(o, (int64_t)kNhwcGroup * NB * 4);
-  if (!(y1 >= y0 && x1 >= x0)) {  // no valid sample: every bin is 0
-    for (int e = lane; e < kNhwcGroup * NB / 4; e += kWave)
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, orr, e * 16, 0, kStAux);
-    return;
-  }
-  const bool dy = y1 - y0 + 1 <= NLY, dx = x1 - x0 + 1 <= NLX;
-  const int R = dy ? y1 - y0 + 1 : NLY, Cs = dx ? x1 - x0 + 1 : NLX;
-  // per-lane sample data: slab indices (row of y sample / column of x sample) and factors,
-  // zeroed (and pointed at index 0) for invalid samples
-  const int i0 = !tv ? 0 : (isy ? (dy ? t.lo - y0 : 2 * s) : (dx ? t.lo - x0 : 2 * s));
-  const int i1 = !tv ? 0 : (isy ? (dy ? t.hi - y0 : 2 * s + 1) : (dx ? t.hi - x0 : 2 * s + 1));
-  const float fl = tv ? t.l : 0.f, fh = tv ? t.h : 0.f;
-  // tap-list source rows / columns: list entry e of an axis is tap (e & 1 ? hi : lo) of sample e / 2
-  // (the source lane supplies both taps; the destination picks by its own parity)
-  const int ysrc_e = (lane < NLY) ? lane : 0, xsrc_e = (lane < NLX) ? lane : 0;
-  const int ylo_s = __shfl(tv ? t.lo : y0, ysrc_e >> 1, kWave), yhi_s = __shfl(tv ? t.hi : y0, ysrc_e >> 1, kWave);
-  const int xlo_s = __shfl(tv ? t.lo : x0, 32 + (xsrc_e >> 1), kWave);
-  const int xhi_s = __shfl(tv ? t.hi : x0, 32 + (xsrc_e >> 1), kWave);
-  const int ysrc = (ysrc_e & 1) ? yhi_s : ylo_s, xsrc = (xsrc_e & 1) ? xhi_s : xlo_s;
-  const int64_t sy = lv.sy[l], sx = lv.sx[l];
-  const float* base = lv.feat[l] + (int64_t)g.b * lv.sb[l];
-  const __amdgpu_buffer_rsrc_t fr =
-      uniform_rsrc(base, ((int64_t)(H - 1) * sy + (int64_t)(W - 1) * sx + c.C) * 4);
-  const int rows_cap = kCells / Cs;  // >= 2: Cs <= NLX
-  const uint32_t inv = (65536u + (uint32_t)Cs - 1u) / (uint32_t)Cs;  // e / Cs for e < 1024
-  const int quad = (lane & 15) * 16, soff = grp * kNhwcGroup * 4;
-  int band_lo = 0, band_hi = 0;
-  if (kStamp) t_pro = (int64_t)__builtin_amdgcn_s_memrealtime();
-  // sample row sr (in order): stage its band if needed, then acc[px] += its two samples of each bin column
-  auto row = [&](int sr, float (&acc)[PW]) {
-    // opaque copies: the broadcasts are re-read per row, not hoisted into ~60 live SGPRs
-    int a0 = i0, a1 = i1, av = tv;
-    float al = fl, ah = fh;
-    asm volatile("" : "+v"(a0), "+v"(a1), "+v"(av), "+v"(al), "+v"(ah));
-    int r0 = __builtin_amdgcn_readlane(a0, sr), r1 = __builtin_amdgcn_readlane(a1, sr);
-    const float ly = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(al), sr));
-    const float hy = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ah), sr));
-    if (!__builtin_amdgcn_readlane(av, sr) && band_hi > band_lo) r0 = r1 = band_lo;  // zero weights: any cell
-    if (r0 < band_lo || r1 >= band_hi) {  // stage the band of slab rows [r0, r0 + rows_cap)
-      band_lo = r0;
-      band_hi = min(r0 + rows_cap, R);
-      const int ncell = (band_hi - band_lo) * Cs;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the previous band's tap reads are done
-      __builtin_amdgcn_wave_barrier();
-      for (int i = 0; 4 * i < ncell; ++i) {
-        int e = 4 * i + (lane >> 4);
-        e = e < ncell ? e : ncell - 1;
-        const int rr = (int)(((uint32_t)e * inv) >> 16), cc = e - rr * Cs;
-        const int yy = dy ? y0 + band_lo + rr : __shfl(ysrc, band_lo + rr, kWave);
-        const int xx = dx ? x0 + cc : __shfl(xsrc, cc, kWave);
-        lds_dma_at<16, 0>(fr, sbase + 1024u * (uint32_t)i, (int)(((int64_t)yy * sy + (int64_t)xx * sx) * 4) + quad,
-                          soff);
-      }
-      wait_vmcnt<0>();
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (kStamp) {
-        if (n_bands == 0) t_land = (int64_t)__builtin_amdgcn_s_memrealtime(), first_cells = ncell;
-        ++n_bands;
-      }
-    }
-    const float* row0 = slab + (r0 - band_lo) * Cs * kNhwcGroup + lane;
-    const float* row1 = slab + (r1 - band_lo) * Cs * kNhwcGroup + lane;
-#pragma unroll
-    for (int ix = 0; ix < 2 * PW; ++ix) {
-      const int q0 = __builtin_amdgcn_readlane(a0, 32 + ix) * kNhwcGroup;
-      const int q1 = __builtin_amdgcn_readlane(a1, 32 + ix) * kNhwcGroup;
-      const float lx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(al), 32 + ix));
-      const float hx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ah), 32 + ix));
-      const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-      const float val = ((w1 * row0[q0] + w2 * row0[q1]) + w3 * row1[q0]) + w4 * row1[q1];
-      acc[ix >> 1] = acc[ix >> 1] + val;
-    }
-  };
-  float* ob = kRegOut ? slab : obuf;  // [channel][bin]
-  if constexpr (kRegOut) {
-    // the 7 x 7 outputs of this lane's channel in VGPRs: a dynamic bin-row loop shifts each
-    // row's results into the tail of outv (static indices only), then out through the slab
-    float outv[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) outv[j] = 0.0f;
-    for (int py = 0; py < PH; ++py) {
-      float acc[PW];
-#pragma unroll
-      for (int px = 0; px < PW; ++px) acc[px] = 0.0f;
-      row(2 * py, acc);
-      row(2 * py + 1, acc);
-#pragma unroll
-      for (int j = 0; j < NB - PW; ++j) outv[j] = outv[j + PW];
-#pragma unroll
-      for (int px = 0; px < PW; ++px) outv[NB - PW + px] = acc[px] * 0.25f;  // count 4: / 4 == * 0.25
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int j = 0; j < NB; ++j) ob[lane * NB + j] = outv[j];  // stride NB (odd): no bank conflicts
-  } else {
-    for (int py = 0; py < PH; ++py) {
-      float acc[PW];
-#pragma unroll
-      for (int px = 0; px < PW; ++px) acc[px] = 0.0f;
-      row(2 * py, acc);
-      row(2 * py + 1, acc);
-#pragma unroll
-      for (int px = 0; px < PW; ++px) ob[lane * NB + py * PW + px] = acc[px] * 0.25f;
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (kStamp) t_eval = (int64_t)__builtin_amdgcn_s_memrealtime();
-  const float4* s4 = reinterpret_cast<const float4*>(ob);
-  for (int e = lane; e < kNhwcGroup * NB / 4; e += kWave) {
-    const float4 q = s4[e];
-    __builtin_amdgcn_raw_buffer_store_b128(
-        u32x4{__float_as_uint(q.x), __float_as_uint(q.y), __float_as_uint(q.z), __float_as_uint(q.w)}, orr, e * 16, 0,
-        kStAux);
-  }
-  if (kStamp && lane == 0) {
-    int64_t* st = reinterpret_cast<int64_t*>(out + c.K * c.C * NB) + (int64_t)w * 8;
-    st[0] = t_start;
-    st[1] = t_pro;
-    st[2] = t_land;
-    st[3] = t_eval;
-    st[4] = (int64_t)__builtin_amdgcn_s_memrealtime();
-    st[5] = n_bands;
-    st[6] = first_cells;
-    st[7] = blockIdx.x & 7;
-  }
 }
 
 static inline int32_t make_levels(int32_t L, const float* const* feats, float* const* grads, const int32_t* feat_hw,
@@ -2887,7 +2128,6 @@ static inline int32_t roi_common_checks(int32_t batch, int32_t channels, int64_t
 struct FwdCaps {
   bool buf;    // 32-bit byte offsets within every (image, level) slice, sampling 2, ph*pw <= 256
   bool lds;    // + ph*pw <= 64 and 2*ph, 2*pw <= 64
-  bool x4;     // + unit x stride, 16-B aligned rows / channel planes / bases (16-B LDS-DMA)
 };
 
 static inline FwdCaps fwd_caps(const RoiLevels& lv, int32_t channels, int32_t ph, int32_t pw, int32_t sr) {
@@ -2899,27 +2139,7 @@ static inline FwdCaps fwd_caps(const RoiLevels& lv, int32_t channels, int32_t ph
     f.buf = f.buf && lv.sc[l] >= 0 && lv.sy[l] >= 0 && lv.sx[l] >= 0 && ext < ((int64_t)1 << 31);
   }
   f.lds = f.buf && ph * pw <= 64 && 2 * ph <= 64 && 2 * pw <= 64;
-  f.x4 = f.lds;
-  for (int l = 0; l < lv.L; ++l)
-    f.x4 = f.x4 && lv.sx[l] == 1 && lv.sy[l] % 4 == 0 && lv.sc[l] % 4 == 0 && lv.sb[l] % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(lv.feat[l]) & 15) == 0;
   return f;
-}
-
-
-// kernels of the product's forward, chosen by shape class
-constexpr int kNhwcCells = 56;  // slab cells of the channels-last kernel (14 KB + 12.25 KB of outputs per wave)
-
-// channels-last features: unit channel stride, 16-B aligned cells, 64-channel groups
-static inline bool nhwc_ok(const RoiLevels& lv, int32_t channels, int32_t ph, int32_t pw, int32_t sr) {
-  if (sr != 2 || ph != 7 || pw != 7 || channels % kNhwcGroup != 0) return false;
-  for (int l = 0; l < lv.L; ++l) {
-    const int64_t ext = ((int64_t)(lv.h[l] - 1) * lv.sy[l] + (int64_t)(lv.w[l] - 1) * lv.sx[l] + channels) * 4;
-    if (lv.sc[l] != 1 || lv.sx[l] < channels || lv.sy[l] < lv.sx[l] || lv.sx[l] % 4 || lv.sy[l] % 4 ||
-        lv.sb[l] % 4 || (reinterpret_cast<uintptr_t>(lv.feat[l]) & 15) || ext >= ((int64_t)1 << 31))
-      return false;
-  }
-  return true;
 }
 
 // channels-last features for the quad kernel: unit channel stride, C % 4 == 0, 16-B aligned

@@ -719,8 +719,10 @@ def _rois(seed, n, batch):
 
 @pytest.mark.parametrize('layout', ['nchw', 'nhwc'])
 def test_roi_align_forward_default_vs_oracle_p2(dev, layout):
-    """The product forward (channel-pair kernel) on P2-sized maps, 600 RoIs incl. border /
-    degenerate / outside ones, against the oracle: bit-identical."""
+    """The product forward on P2-sized maps, 600 RoIs incl. border / degenerate / outside ones,
+    against the oracle: bit-identical.  C = 96: NCHW runs the channel-pair kernel, channels-last the
+    band kernel (96 % 64 != 0) on all three of its paths (107 windows of <= 192 cells: quad stages,
+    383 of <= 480: interleaved stages, 109 larger: row bands; 1 without a valid sample)."""
     from frcnn_amd import ops
     grids = [(152, 256), (76, 128), (38, 64), (19, 32)]
     feats = inputs.feature_maps(42, grids, 96, 2)
@@ -743,7 +745,7 @@ def test_roi_align_forward_default_vs_oracle_p2(dev, layout):
 def test_roi_align_forward_bench_config_bit_exact(dev, layout, roi_set):
     """The forward at the bench's own configuration, C = 256, P2-P5 of a 2-image 608x1024
     batch (152x256 ... 19x32), NCHW (channel-pair kernel) and channels-last (the FPN's NHWC
-    levels: channel-quad kernel), on three RoI sets: the 1024 RoIs of a random-init cfg2
+    levels: channel-group kernel), on three RoI sets: the 1024 RoIs of a random-init cfg2
     step (cfg2_rois.npz, 873 / 102 / 42 / 7 on P2..P5: tiny), VOC-sized RoIs in the RCNN
     sampler's mix around the bench images' gts (cfg2_rois_voc.npz, gen_voc_rois.py: 235 /
     369 / 219 / 201, tap grids up to 27 x 29 cells) and the RoIs of a `bench.py --mode
@@ -800,7 +802,10 @@ def test_roi_align_channel_group_kernel_vs_oracle(dev, pooled, C):
     one 4-wave workgroup per (RoI, 64 channels), 120-cell slab, bands of bin rows, list-row bands
     for bin rows spanning more rows than the slab holds) against the oracle, bit-identical: random
     RoIs over four levels (windows from 1 cell to 28 x 28, single- and multi-band), pathological
-    RoIs on a 10 x 30 level, pooled sizes 1x1 .. 7x7 (8x8: the band kernel, cg_ok)."""
+    RoIs on a 10 x 30 level, pooled sizes 1x1 .. 7x7.  8x8 bins reach none of the staged kernels:
+    16 * 8 tap-list columns exceed the 120-cell slab (cg_ok) and quad_max_cells(8, 8) = 1056 cells
+    the 832 of the quad and pair slabs (quad_ok, pair_ok), so that case runs the per-RoI LDS-window
+    kernel (roi_align_fwd_lds_kernel) on channels-last features."""
     from frcnn_amd import ops
     grids = [(76, 128), (38, 64), (19, 32), (10, 30)]
     feats = inputs.feature_maps(60, grids, C, 2)
@@ -811,6 +816,29 @@ def test_roi_align_channel_group_kernel_vs_oracle(dev, pooled, C):
     ref = oracle.roi_align(feats, rois, levels, scales, pooled, 2)
     ft = [T(f, dev).contiguous(memory_format=torch.channels_last) for f in feats]
     out = ops.roi_align_multilevel(ft, T(rois, dev), T(levels, dev), scales, pooled, 2).cpu().numpy()
+    np.testing.assert_array_equal(out, ref)
+
+
+@pytest.mark.parametrize('C', [16, 40])
+def test_roi_align_standalone_quad_kernel_vs_oracle(dev, C):
+    """The standalone channel-quad forward (roi_align_fwd_quad_kernel): channels-last levels whose
+    shape neither the channel-group kernel (C % 64 != 0) nor the band kernel takes -- 4 x 12 bins:
+    quad_max_cells(4, 12) = 16 * 49 = 784 <= 832 (quad_ok), but a band of 5 rows of the 49-column
+    window needs 245 > 240 cells (band_fits).  Against the oracle, bit-identical: random, border and
+    degenerate RoIs on a 19 x 32 level, pathological ones on a 10 x 30 level, and three wide RoIs, so
+    that windows of every stage depth occur (<= 192 cells: 4 quads per stage, <= 384: 2, above: 1);
+    C = 40 adds a second and a partial third 16-channel chunk."""
+    from frcnn_amd import ops
+    grids = [(19, 32), (10, 30)]
+    feats = inputs.feature_maps(70, grids, C, 2)
+    wide = np.array([[1, 0, 0, 119, 39], [0, 2, 1, 110, 38], [1, 30, 20, 1000, 500]], np.float32)
+    rois = np.concatenate([_rois(71, 40, 2), wide[2:], _pathological_rois(2), wide[:2]], 0)
+    levels = np.zeros(len(rois), np.int64)
+    levels[-13:] = 1  # the pathological and the first two wide RoIs on the 10 x 30 level
+    scales = [1 / 32, 1 / 4]
+    ref = oracle.roi_align(feats, rois, levels, scales, (4, 12), 2)
+    ft = [T(f, dev).contiguous(memory_format=torch.channels_last) for f in feats]
+    out = ops.roi_align_multilevel(ft, T(rois, dev), T(levels, dev), scales, (4, 12), 2).cpu().numpy()
     np.testing.assert_array_equal(out, ref)
 
 

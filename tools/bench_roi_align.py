@@ -21,9 +21,11 @@ import bench  # noqa: E402
 from frcnn_amd import ops, _lib, set_sampler_mode  # noqa: E402
 import toolslib  # noqa: E402
 
-STAMPED = {1, 9, 15}
+STAMPED = {1, 9, 68}  # pair / quad / band kernel stamped builds: 8 int64 per 16-channel item
 STAMPED_NHWC = {6}  # channels-last stamped build: 8 int64 per 64-channel item
-NHWC = set(range(2, 71)) | set(range(80, 100))  # channels-last kernels: run on channels_last copies of the same features
+STAMPED_CG = {94}  # channel-group stamped build: 16 int64 per 64-channel item
+# channels-last kernels: run on channels_last copies of the same features
+NHWC = set(range(2, 12)) | {19, 23, 24, 25, 65, 68, 89, 90, 91} | set(range(94, 100))
 
 
 def calibrate(variants, dev, small=False):
@@ -94,7 +96,12 @@ def nhwc_stamps_report(stm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--variants', default='0')
+    ap.add_argument('--variants', default='0',
+                    help='tools forward variants (frh_roi_align_fwd_variant; parameters in tools/csrc/roi_lab.hip): '
+                    '0 / 1 pair kernel / stamped; 2-7 lane = channel lab kernel (6 stamped); 8-11, 25 quad kernel '
+                    '(9 stamped, 11 5 waves per SIMD, 25 16-KB slab); 19, 23, 24 quad lab kernels; 65 / 68 band kernel '
+                    '/ stamped; 89 / 94 channel-group kernel / stamped, 90, 91, 95 other slabs and wave counts; 96-99 '
+                    'software-pipelined channel-group lab kernel')
     ap.add_argument('--rounds', type=int, default=1)
     ap.add_argument('--cold', action='store_true')
     ap.add_argument('--after-write', action='store_true',
@@ -139,6 +146,8 @@ def main():
         extra = (K * C // 16) * 16 if v in STAMPED else 0  # 8 int64 stamps per 16-channel item
         if v in STAMPED_NHWC:
             extra = (K * C // 64 + 8) * 16
+        if v in STAMPED_CG:
+            extra = (K * C // 64) * 32
         full = torch.zeros(K * C * ph * pw + extra, device=dev)
         out = full[:K * C * ph * pw].view(K, C, ph, pw)
 
@@ -194,6 +203,9 @@ def main():
             stamps_report(full[K * C * ph * pw:].view(torch.int64).view(-1, 8).cpu().numpy())
         if v in STAMPED_NHWC:
             nhwc_stamps_report(full[K * C * ph * pw:].view(torch.int64).view(-1, 8)[:K * C // 64].cpu().numpy())
+        if v in STAMPED_CG:
+            from bench_roi_sets import cg_stamps_report
+            cg_stamps_report(full[K * C * ph * pw:].view(torch.int64).cpu().numpy())
         if ref is None:
             ref = out.clone()
         same = bool(torch.equal(out, ref))

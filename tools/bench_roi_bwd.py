@@ -28,8 +28,9 @@ def main():
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--json')
     ap.add_argument('--variants', default='', help='tools backward variants (frh_roi_align_bwd_variant) beside the '
-                    'product: 0 nhwc float, 1 register-resident float, 2 nhwc fixed, 3 register-resident fixed, 4 / 5 '
-                    'readlane tap lists float / fixed')
+                    'product: 0 / 2 product kernel with one wave per RoI, float / fixed; 1 / 3 register-resident lab '
+                    'kernel, float / fixed; 4 / 5 readlane lab kernel, float / fixed; 6-8 its diagnostics (plain stores, no '
+                    'column loop, setup only); 9 / 10 / 11 product kernel with 2 / 4 / 8 waves; 12 with 4, fixed')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     out = {}

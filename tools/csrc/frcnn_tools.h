@@ -1,7 +1,7 @@
 // TOOLS-ONLY entry points (tools/lib/libfrcnn_tools.so; never linked into the product
-// library).  RoIAlign forward laboratory: the product's forward kernel and a per-wave
-// timestamped build of it (tools/bench_roi_align.py); the NMS scan's stamped build
-// (tools/bench_nms.py).
+// library).  RoIAlign laboratory: the product's kernels at other slab sizes / wave counts, their
+// per-item timestamped builds and the kernels measured and not adopted (tools/bench_roi_align.py,
+// bench_roi_sets.py, bench_roi_bwd.py); the NMS scan's stamped build (tools/bench_nms.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,10 +10,17 @@
 extern "C" {
 #endif
 
-/* variant 0: frh_roi_align_fwd_strided's pair kernel; 1: the same with per-item stamps (8
- * int64 per item after the output).  Arguments as frh_roi_align_fwd_strided, plus a
- * workspace of frh_roi_align_workspace bytes (unused by these two). */
-/* round-6 backward A/B: 0 nhwc float, 1 register-resident float, 2 / 3 the same in fixed point */
+/* Forward variants (the list with each one's parameters: roi_lab.hip).  0: frh_roi_align_fwd_strided's
+ * pair kernel; 1: the same with per-item stamps (8 int64 per item after the output); 2-7 lane =
+ * channel lab kernel; 8-11, 25 quad kernel (9 stamped); 19 shared-setup quad lab kernel; 23 / 24
+ * persistent quad lab kernel; 65 band kernel as dispatched, 68 stamped; 89 channel-group kernel
+ * as dispatched, 94 stamped (16 int64 per item), 90 / 91 / 95 other slabs / wave counts; 96-99
+ * software-pipelined channel-group lab kernel.  Retired (the call fails): 12-18, 20, 26-64, 66, 67,
+ * 80-88, 92, 93.  Arguments as frh_roi_align_fwd_strided, plus a workspace of
+ * frh_roi_align_workspace bytes (unused by the live variants). */
+/* Backward variants (channels-last gradients, 7 x 7 bins): 0 / 2 the product kernel with one wave per
+ * RoI, float / fixed point; 1 / 3 register-resident lab kernel; 4 / 5 readlane lab kernel, 6-8 its
+ * diagnostics; 9 / 10 / 11 the product kernel with 2 / 4 / 8 waves, 12 with 4 in fixed point. */
 int32_t frh_roi_align_bwd_variant(int32_t variant, int32_t num_levels, float* const* grad_feats,
                                   int64_t* const* acc_feats, const int32_t* feat_hw, const int64_t* strides,
                                   const float* scales, int32_t batch, int32_t channels, const float* rois,

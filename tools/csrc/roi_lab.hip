@@ -1,6 +1,23 @@
-// TOOLS-ONLY RoIAlign forward laboratory (see frcnn_tools.h).  Variant 0 is the product's
-// instantiation, so A/B runs compare against exactly what ships; 1 is its per-wave stamped
-// build.
+// TOOLS-ONLY RoIAlign laboratory (see frcnn_tools.h).  The product kernels (csrc/roi_kernels.h)
+// are frozen to their shipped forms; a variant here is either one of them at another value of its
+// surviving knobs (slab size, waves per SIMD, waves per workgroup, stamped build) or a kernel
+// measured and not adopted (roi_lab_kernels.h).  Variants whose knob was frozen are retired: the
+// number stays reserved (roi_align.hip and profiles/ cite it) and the call fails.
+//
+// Forward variants (frh_roi_align_fwd_variant):
+//   0 / 1    the pair kernel as dispatched / its stamped build
+//   2-7      lab kernel roi_align_fwd_nhwc_kernel: 56 / 64 / 96 slab cells, 5 outputs in LDS,
+//            6 stamped, 7 128 cells
+//   8-11     quad kernel: 8 and 10 as dispatched (3 waves per SIMD), 9 stamped, 11 5 waves per SIMD
+//   19       lab kernel roi_align_fwd_quad4_kernel (RoI setup shared by a 4-wave workgroup)
+//   23 / 24  lab kernel roi_align_fwd_quadp_kernel (software-pipelined persistent), 8 / 12 waves per CU
+//   25       quad kernel with a 16-KB slab
+//   65 / 68  band kernel as dispatched / its stamped build
+//   89       channel-group kernel as dispatched (4 waves, 120 cells, 5 waves per SIMD); 94 stamped
+//   90       4 waves, 144 cells, registers as compiled; 91 8 waves, 120 cells; 95 124 cells
+//   96-99    lab kernel roi_align_fwd_cgp_kernel (software-pipelined items): 2 / 3 / 4 items at
+//            144 cells; 99: 2 at 116 cells
+// Retired: 12-18, 20, 26-64, 66, 67, 80-88, 92, 93.
 #include "frcnn_tools.h"
 #include "roi_kernels.h"
 #include "roi_lab_kernels.h"
@@ -9,12 +26,20 @@ using namespace frh;
 
 extern "C" size_t frh_roi_align_workspace(int64_t num_rois) { return (size_t)(num_rois > 0 ? num_rois : 1) * 64; }
 
+static bool fwd_variant_retired(int v) {
+  return (v >= 12 && v <= 18) || v == 20 || (v >= 26 && v <= 64) || v == 66 || v == 67 || (v >= 80 && v <= 88) ||
+         v == 92 || v == 93;
+}
+
 extern "C" int32_t frh_roi_align_fwd_variant(int32_t variant, int32_t num_levels, const float* const* feats,
                                              const int32_t* feat_hw, const int64_t* strides, const float* scales,
                                              int32_t batch, int32_t channels, const float* rois,
                                              const int64_t* roi_levels, int64_t num_rois, int32_t pooled_h,
                                              int32_t pooled_w, int32_t sampling_ratio, int32_t aligned, float* out,
                                              void* workspace, size_t ws_bytes, void* stream) {
+  FRH_REQUIRE(!fwd_variant_retired(variant),
+              "roi_align variant %d retired: its kernel parameter is frozen to the shipped value (last built at commit "
+              "d6bef71)", variant);
   int32_t r = roi_common_checks(batch, channels, num_rois, pooled_h, pooled_w, rois);
   if (r) return r;
   FRH_REQUIRE((feats && out) || num_rois == 0, "null pointer argument");
@@ -37,183 +62,36 @@ extern "C" int32_t frh_roi_align_fwd_variant(int32_t variant, int32_t num_levels
     hipLaunchKernelGGL((roi_align_fwd_quadp_kernel<kCpolNT>), gq, dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
-  if (variant >= 28 && variant <= 70) {  // band kernel: 28 product (208 cells), 29 stamped, 30 176 cells,
-                                         // 31 256 cells, 32 208 cells at 4 waves per SIMD
+  if (variant == 65 || variant == 68) {  // the band kernel as dispatched (240 cells); 68: stamped (8 int64 per item)
     const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
-    FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w) && band_fits(pooled_h, pooled_w, 160),
+    FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w) && band_fits(pooled_h, pooled_w, 240),
                 "the band kernel does not take this shape");
-    const int64_t tq = num_rois * ((channels + 4 * kQuadWave - 1) / (4 * kQuadWave));
+    const int64_t tq = num_rois * ((channels + kQuadChunk - 1) / kQuadChunk);
     const dim3 gq((unsigned)(8 * ((tq + 7) / 8)));
-    if (variant == 28)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 29)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, true, 208>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 30)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 176>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 31)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 256>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 32)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 4>), gq, dim3(kWave), 0, st, lv, c,
-                         out);
-    else if (variant == 33)  // no quad rotation
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 0>), gq, dim3(kWave), 0, st, lv,
-                         c, out);
-    else if (variant == 34)  // rotation, per-step stores
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 2>), gq, dim3(kWave), 0, st, lv,
-                         c, out);
-    else if (variant == 35)  // hybrid: small windows by the quad path
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 1, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 36)  // hybrid, 160-cell slab (10 KB)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 160, false, 3, 1, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 37)  // hybrid, 160-cell slab, 4 waves per SIMD
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 160, false, 4, 1, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 38)  // hybrid, bands without quad rotation
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 0, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 39)  // hybrid, bands without rotation, stamped
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, true, 208, false, 3, 0, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 40)  // hybrid up to the quad path's D = 2 windows (<= 384 cells), bands above
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 0, 2>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 41)  // hybrid (D = 4), 232-cell slab: 8-row bands
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 0, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 42)  // hybrid (D = 2), 232-cell slab
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 0, 2>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 43)  // hybrid (D = 4), 232-cell slab, rotated quads in the bands
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 1, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 44)  // hybrid (D = 4), 256-cell slab
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 256, false, 3, 0, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 46)  // hybrid (D = 4), 232-cell slab, stores after the last band
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 47)  // product + windows above 464 cells (3+ bands) by the quad stages
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 464>), gq, dim3(kWave), 0,
-                         st, lv, c, out);
-    else if (variant == 48)  // product + windows above 348 cells by the quad stages
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 348>), gq, dim3(kWave), 0,
-                         st, lv, c, out);
-    else if (variant == 49)  // product + windows above 696 cells by the quad stages
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 696>), gq, dim3(kWave), 0,
-                         st, lv, c, out);
-    else if (variant == 50)  // product + two-quad interleaved whole-window stages up to 464 cells
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 0, 2>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 51)  // as 50, windows above 696 cells by the quad stages
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 696, 2>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 52)  // as 50 plus one [cell][4 quads] stage for windows <= 232 cells
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 0, 3>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 53)  // as 50, the quad D = 4 stage off (bands below 232 cells are unreachable)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 0, 0, 3>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 54)  // the product's paths on a 208-cell slab (13 KB: 12 waves per CU by LDS)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 3, 3, 4, 0, 2>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 55)  // as 54, 4 waves per SIMD requested
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 208, false, 4, 3, 4, 0, 2>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 56)  // the product kernel, stamped (8 int64 per item after the output)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, true, 232, false, 3, 3, 4, 0, 2>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 57 || variant == 58) {  // the product's paths, one wave per (RoI, chunk pair); 58 stamped
-      const int64_t tp = num_rois * (((channels + 4 * kQuadWave - 1) / (4 * kQuadWave) + 1) / 2);
-      const dim3 gp((unsigned)(8 * ((tp + 7) / 8)));
-      if (variant == 57)
-        hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 0, 2, 2>), gp,
-                           dim3(kWave), 0, st, lv, c, out);
-      else
-        hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, true, 232, false, 3, 3, 4, 0, 2, 2>), gp,
-                           dim3(kWave), 0, st, lv, c, out);
-    }
-    else if (variant == 59)  // the product kernel with the chunk-major item order (round 4's quad kernel order)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 232, false, 3, 3, 4, 0, 2, 1, 0>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 62)  // the product's paths on a 240-cell slab (15 KB: the same LDS as the declared 232-cell one)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 240, false, 3, 3, 4, 0, 2>), gq, dim3(kWave),
-                         0, st, lv, c, out);
-    else if (variant == 63)  // round 6: the product + kFwdTrim (no loads for lanes past the window, no empty rounds)
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 240, false, 3, 3, 4, 0, 2, 1, 1, kFwdTrim>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 64)  // round 6: the product + the interleaved path's quad rotation
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 240, false, 3, 3, 4, 0, 2, 1, 1, kFwdIlvRot>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 66) {  // round 6: the product (trim + rotation) on spatially sorted RoI records
-      FRH_REQUIRE(workspace && ws_bytes >= (size_t)num_rois * 32, "workspace too small");
-      RoiCfg cs = c;
-      cs.rec = reinterpret_cast<const int32_t*>(workspace);
-      hipLaunchKernelGGL(roi_sort_kernel, dim3(1), dim3(kSortThreads), 0, st, lv, c,
-                         reinterpret_cast<int32_t*>(workspace));
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 240, false, 3, 3, 4, 0, 2, 1, 1,
-                                                    kFwdTrim | kFwdIlvRot | kFwdSorted>), gq, dim3(kWave), 0, st, lv,
-                         cs, out);
-    }
-    else if (variant == 67) {  // the sort kernel alone (its cost in the variant-66 sum)
-      FRH_REQUIRE(workspace && ws_bytes >= (size_t)num_rois * 32, "workspace too small");
-      hipLaunchKernelGGL(roi_sort_kernel, dim3(1), dim3(kSortThreads), 0, st, lv, c,
-                         reinterpret_cast<int32_t*>(workspace));
-    }
-    else if (variant == 65)  // round 6: trim + rotation
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, false, 240, false, 3, 3, 4, 0, 2, 1, 1,
-                                                    kFwdTrim | kFwdIlvRot>), gq, dim3(kWave), 0, st, lv, c, out);
-    else  // 45: hybrid (D = 4), 232-cell slab, stamped
-      hipLaunchKernelGGL((roi_align_fwd_band_kernel<kCpolNT, true, 232, false, 3, 0, 4>), gq, dim3(kWave), 0, st,
-                         lv, c, out);
+    if (variant == 65)
+      hipLaunchKernelGGL((roi_align_fwd_band_kernel<240, false, false>), gq, dim3(kWave), 0, st, lv, c, out);
+    else
+      hipLaunchKernelGGL((roi_align_fwd_band_kernel<240, false, true>), gq, dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
-  if (variant >= 80 && variant <= 99) {  // round 6: channel-group kernel, one workgroup per (RoI, 64 channels)
-    // 80: 4 waves, 144-cell slab (36 KB); 81: 8 waves, 144; 82: 4 waves, 192 cells; 83: 2 waves, 144;
-    // 84: 8 waves, 192; 85: 4 waves, 160
+  if ((variant >= 89 && variant <= 91) || (variant >= 94 && variant <= 99)) {  // channel-group kernel
     const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
-    FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w) && cg_ok(channels, pooled_h, pooled_w, 112),
+    FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w) && cg_ok(channels, pooled_h, pooled_w, 116),
                 "the channel-group kernel does not take this shape");
     const int64_t tg = num_rois * (channels / kCgChan);
     const dim3 gg((unsigned)(8 * ((tg + 7) / 8)));
-    if (variant == 80)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 144>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 81)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<8, 144>), gg, dim3(8 * kWave), 0, st, lv, c, out);
-    else if (variant == 82)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 192>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 83)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<2, 144>), gg, dim3(2 * kWave), 0, st, lv, c, out);
-    else if (variant == 84)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<8, 192>), gg, dim3(8 * kWave), 0, st, lv, c, out);
-    else if (variant == 85)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 160>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 86)  // 120-cell slab (30 KB: 5 workgroups per CU by LDS), <= 96 VGPRs (5 waves per SIMD)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120, kCpolNT, false, 5>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 87)  // 120-cell slab, registers as compiled (4 waves per SIMD)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 88)  // 112-cell slab (28 KB), 5 waves per SIMD
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 112, kCpolNT, false, 5>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 89)  // 120 cells, 5 waves per SIMD, one sample row's taps in flight
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120, kCpolNT, false, 5, false>), gg, dim3(4 * kWave), 0, st, lv,
-                         c, out);
-    else if (variant == 90)  // 144 cells, one sample row's taps in flight
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 144, kCpolNT, false, 0, false>), gg, dim3(4 * kWave), 0, st, lv,
-                         c, out);
-    else if (variant == 92)  // as 90, RoI-major item order
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 144, kCpolNT, false, 0, false, 1>), gg, dim3(4 * kWave), 0, st,
-                         lv, c, out);
-    else if (variant == 93)  // as 90, default store policy
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 144, 0, false, 0, false>), gg, dim3(4 * kWave), 0, st, lv, c, out);
-    else if (variant == 94)  // variant 89 (120 cells, 5 waves per SIMD, one sample row in flight), stamped (8 int64 per item after the output)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120, kCpolNT, false, 5, false, 0, true>), gg, dim3(4 * kWave), 0,
-                         st, lv, c, out);
-    else if (variant == 95)  // 124 cells (31 KB: 5 workgroups per CU), 5 waves per SIMD, one sample row in flight
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 124, kCpolNT, false, 5, false>), gg, dim3(4 * kWave), 0, st, lv,
-                         c, out);
-    else if (variant >= 96 && variant <= 99) {  // software-pipelined, kItems items per workgroup:
-                                                 // 96 / 97 / 98: 2 / 3 / 4 items at 144 cells; 99: 2 at 116 cells
+    if (variant == 89)  // as dispatched: 120 cells (30 KB: 5 workgroups per CU by LDS), 5 waves per SIMD
+      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120, false, 5>), gg, dim3(4 * kWave), 0, st, lv, c, out);
+    else if (variant == 90)  // 144 cells, registers as compiled
+      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 144, false, 0>), gg, dim3(4 * kWave), 0, st, lv, c, out);
+    else if (variant == 91)  // 8 waves, 120 cells (2 workgroups per CU)
+      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<8, 120, false, 5>), gg, dim3(8 * kWave), 0, st, lv, c, out);
+    else if (variant == 94)  // variant 89, stamped (16 int64 per item after the output)
+      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 120, false, 5, true>), gg, dim3(4 * kWave), 0, st, lv, c, out);
+    else if (variant == 95)  // 124 cells (31 KB: 5 workgroups per CU), 5 waves per SIMD
+      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<4, 124, false, 5>), gg, dim3(4 * kWave), 0, st, lv, c, out);
+    else {  // 96-99, software-pipelined, kItems items per workgroup:
+            // 96 / 97 / 98: 2 / 3 / 4 items at 144 cells; 99: 2 at 116 cells
       const int ki = variant == 96 || variant == 99 ? 2 : variant == 97 ? 3 : 4;
       const int64_t per = (tg + 7) / 8, nwx = (per + ki - 1) / ki;
       const dim3 gp((unsigned)(8 * nwx));
@@ -227,75 +105,36 @@ extern "C" int32_t frh_roi_align_fwd_variant(int32_t variant, int32_t num_levels
         hipLaunchKernelGGL((roi_align_fwd_cgp_kernel<4, 116, 2, kCpolNT, false, 5>), gp, dim3(4 * kWave), 0, st, lv, c,
                            out);
     }
-    else  // 91: 8 waves, 144 cells, one sample row's taps in flight, 4 waves per SIMD (2 workgroups per CU)
-      hipLaunchKernelGGL((roi_align_fwd_cg_kernel<8, 120, kCpolNT, false, 5, false>), gg, dim3(8 * kWave), 0, st, lv,
-                         c, out);
-    return check_launch("frh_roi_align_fwd_variant");
-  }
-  if (variant == 26 || variant == 27) {  // quad kernel, chunk-pair-major item order (27: + stamps)
-    const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
-    FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w), "the quad kernel does not take this shape");
-    const int64_t tq = num_rois * ((channels + 4 * kQuadWave - 1) / (4 * kQuadWave));
-    const dim3 gq((unsigned)(8 * ((tq + 7) / 8)));
-    if (variant == 26)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, kQuadWave, 0, false, kQuadSlab, 1>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
-    else
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, true, 3, kQuadWave, 0, false, kQuadSlab, 1>), gq,
-                         dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
   if (variant == 25) {  // quad kernel with a 16-KB slab (10 waves per CU by LDS; D = 4 up to 256 cells)
     const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
     FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w, QuadLayout<1, 4096>::kCells),
                 "the quad kernel does not take this shape");
-    const int64_t tq = num_rois * ((channels + 4 * kQuadWave - 1) / (4 * kQuadWave));
+    const int64_t tq = num_rois * ((channels + kQuadChunk - 1) / kQuadChunk);
     const dim3 gq((unsigned)(8 * ((tq + 7) / 8)));
-    hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, kQuadWave, 0, false, 4096>), gq, dim3(kWave), 0,
-                       st, lv, c, out);
+    hipLaunchKernelGGL((roi_align_fwd_quad_kernel<false, 3, 4096>), gq, dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
-  if (variant == 19 || variant == 20) {  // quad kernel, RoI setup shared by a 4-wave workgroup (20: LDS-staged stores)
+  if (variant == 19) {  // quad kernel, RoI setup shared by a 4-wave workgroup
     const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
     FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w), "the quad kernel does not take this shape");
     const int64_t tq = num_rois * ((channels + 16 * kQuadWave - 1) / (16 * kQuadWave));
     const dim3 gq((unsigned)(8 * ((tq + 7) / 8)));
-    if (variant == 19)
-      hipLaunchKernelGGL((roi_align_fwd_quad4_kernel<kCpolNT, 0>), gq, dim3(4 * kWave), 0, st, lv, c, out);
-    else
-      hipLaunchKernelGGL((roi_align_fwd_quad4_kernel<kCpolNT, 1>), gq, dim3(4 * kWave), 0, st, lv, c, out);
+    hipLaunchKernelGGL(roi_align_fwd_quad4_kernel, gq, dim3(4 * kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
-  if (variant >= 8 && variant <= 18) {  // channels-last quad kernel (9: stamped; 10: 3 waves/SIMD; 11: 5;
-                                        // 12 / 13 / 14: 32 / 64 / 128 channels per item; 15: 32 stamped)
+  if (variant >= 8 && variant <= 11) {  // channels-last quad kernel (8, 10: as dispatched; 9: stamped; 11: 5 waves/SIMD)
     const FwdCaps fq = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
     FRH_REQUIRE(quad_ok(fq, lv, channels, pooled_h, pooled_w), "the quad kernel does not take this shape");
-    const int qw = variant == 12 || variant == 15 ? 8 : variant == 13 ? 16 : variant == 14 ? 32 : kQuadWave;
-    const int64_t tq = num_rois * ((channels + 4 * qw - 1) / (4 * qw));
+    const int64_t tq = num_rois * ((channels + kQuadChunk - 1) / kQuadChunk);
     const dim3 gq((unsigned)(8 * ((tq + 7) / 8)));
-    if (variant == 12)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, 8>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 13)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, 16>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 14)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, 32>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 15)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, true, 3, 8>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 16)  // LDS-staged 16-B output stores
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, 4, 1>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 17)  // no output stores (diagnostic: the staging + evaluation alone)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3, 4, 2>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 18)  // LDS-staged 16-B stores, default cache policy
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<0, false, 3, 4, 1>), gq, dim3(kWave), 0, st, lv, c, out);
+    if (variant == 9)
+      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<true>), gq, dim3(kWave), 0, st, lv, c, out);
+    else if (variant == 11)
+      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<false, 5>), gq, dim3(kWave), 0, st, lv, c, out);
     else
-    if (variant == 8)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 9)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, true>), gq, dim3(kWave), 0, st, lv, c, out);
-    else if (variant == 10)
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 3>), gq, dim3(kWave), 0, st, lv, c, out);
-    else
-      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<kCpolNT, false, 5>), gq, dim3(kWave), 0, st, lv, c, out);
+      hipLaunchKernelGGL((roi_align_fwd_quad_kernel<false, 3>), gq, dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
   if (variant >= 2 && variant <= 7) {  // channels-last kernel: slab cells / outputs in VGPRs or in LDS
@@ -316,24 +155,29 @@ extern "C" int32_t frh_roi_align_fwd_variant(int32_t variant, int32_t num_levels
       hipLaunchKernelGGL((roi_align_fwd_nhwc_kernel<7, 7, 128, kCpolNT, true>), gn, dim3(kWave), 0, st, lv, c, out);
     return check_launch("frh_roi_align_fwd_variant");
   }
+  FRH_REQUIRE(variant == 0 || variant == 1, "roi_align variant %d unknown", variant);
   const FwdCaps f = fwd_caps(lv, channels, pooled_h, pooled_w, sampling_ratio);
   FRH_REQUIRE(pair_ok(f, channels, pooled_h, pooled_w), "the pair kernel does not take this shape");
   const int64_t total = num_rois * ((channels + kPairChunk - 1) / kPairChunk);
   FRH_REQUIRE(total <= (int64_t)0x7fffffff - 7, "too many RoIs");
   const dim3 g1((unsigned)(8 * ((total + 7) / 8)));
   if (variant == 0)
-    hipLaunchKernelGGL((roi_align_fwd_pair_kernel<kCpolNT, false>), g1, dim3(kWave), 0, st, lv, c, out);
-  else if (variant == 1)
-    hipLaunchKernelGGL((roi_align_fwd_pair_kernel<kCpolNT, true>), g1, dim3(kWave), 0, st, lv, c, out);
+    hipLaunchKernelGGL((roi_align_fwd_pair_kernel<false>), g1, dim3(kWave), 0, st, lv, c, out);
   else
-    FRH_REQUIRE(false, "roi_align variant %d unknown", variant);
+    hipLaunchKernelGGL((roi_align_fwd_pair_kernel<true>), g1, dim3(kWave), 0, st, lv, c, out);
   return check_launch("frh_roi_align_fwd_variant");
 }
 
-// Round-6 backward A/B (channels-last gradients, sampling 2, 7 x 7 bins): 0 = the product's
-// roi_align_bwd_nhwc_kernel (float atomics), 1 = roi_align_bwd_nhwc_reg_kernel (grad_out in
-// registers, float atomics), 2 / 3 = the same two in fixed point (absmax pass + conversion, as
-// frh_roi_align_bwd_fixed; accs zeroed by the caller).  grads zeroed by the caller for 0 / 1.
+// Backward A/B (channels-last gradients, sampling 2, 7 x 7 bins); no variant is retired: the
+// product kernel keeps its kFixed and kNW parameters.
+//   0 / 2    the product's roi_align_bwd_nhwc_kernel with one wave per (RoI, 64 channels): float
+//            atomics / fixed point (absmax pass + conversion, as frh_roi_align_bwd_fixed)
+//   1 / 3    lab kernel roi_align_bwd_nhwc_reg_kernel (grad_out in registers): float / fixed point
+//   4 / 5    lab kernel roi_align_bwd_nhwc2_kernel (tap lists read by v_readlane): float / fixed point
+//   6-8      its diagnostics: plain stores instead of atomics / no column loop / setup only
+//   9-11     the product kernel with 2 / 4 (as dispatched) / 8 waves per RoI, float atomics
+//   12       4 waves, fixed point (as frh_roi_align_bwd_fixed dispatches it)
+// accs zeroed by the caller for the fixed-point variants, grads for the others.
 extern "C" int32_t frh_roi_align_bwd_variant(int32_t variant, int32_t num_levels, float* const* grad_feats,
                                              int64_t* const* acc_feats, const int32_t* feat_hw, const int64_t* strides,
                                              const float* scales, int32_t batch, int32_t channels, const float* rois,
@@ -373,21 +217,18 @@ extern "C" int32_t frh_roi_align_bwd_variant(int32_t variant, int32_t num_levels
     hipLaunchKernelGGL(roi_align_bwd_nhwc2_kernel<true>, grid, dim3(kWave), 0, st, lv, c, grad_out);
   else if (variant == 6)  // diagnostic: variant 4 with plain stores instead of atomics (wrong sums)
     hipLaunchKernelGGL((roi_align_bwd_nhwc2_kernel<false, true>), grid, dim3(kWave), 0, st, lv, c, grad_out);
-  else if (variant == 9 || variant == 10 || variant == 11 || variant == 12) {  // product kernel, kNW waves per RoI
-    const dim3 gw((unsigned)num_rois, (unsigned)((channels + kWave - 1) / kWave));
-    if (variant == 9)
-      hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 2>), gw, dim3(2 * kWave), 0, st, lv, c, grad_out);
-    else if (variant == 10)
-      hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 4>), gw, dim3(4 * kWave), 0, st, lv, c, grad_out);
-    else if (variant == 11)
-      hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 8>), gw, dim3(8 * kWave), 0, st, lv, c, grad_out);
-    else
-      hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<true, 4>), gw, dim3(4 * kWave), 0, st, lv, c, grad_out);
-  }
   else if (variant == 7)  // diagnostic: no column loop (row sums stored)
     hipLaunchKernelGGL((roi_align_bwd_nhwc2_kernel<false, true, 1>), grid, dim3(kWave), 0, st, lv, c, grad_out);
   else if (variant == 8)  // diagnostic: setup only (grad_out staging, tap entries, ranks)
     hipLaunchKernelGGL((roi_align_bwd_nhwc2_kernel<false, true, 2>), grid, dim3(kWave), 0, st, lv, c, grad_out);
+  else if (variant == 9)  // product kernel, kNW waves per RoI
+    hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 2>), grid, dim3(2 * kWave), 0, st, lv, c, grad_out);
+  else if (variant == 10)
+    hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 4>), grid, dim3(4 * kWave), 0, st, lv, c, grad_out);
+  else if (variant == 11)
+    hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<false, 8>), grid, dim3(8 * kWave), 0, st, lv, c, grad_out);
+  else if (variant == 12)
+    hipLaunchKernelGGL((roi_align_bwd_nhwc_kernel<true, 4>), grid, dim3(4 * kWave), 0, st, lv, c, grad_out);
   else
     FRH_REQUIRE(false, "backward variant %d unknown", variant);
   if (fixed) {

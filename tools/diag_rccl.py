@@ -1,7 +1,7 @@
 """RCCL on the one-GPU box: a world-size-1 `nccl` process group (RCCL on ROCm)
 with `device_id`, then one of each collective the data-parallel path uses or could use, on
 device tensors, each checked against its exact single-rank result.  Run it under
-`rocprofv3 --kernel-trace` (tools/profile_r06.sh) to list the kernels RCCL itself launches, and
+`rocprofv3 --kernel-trace --stats` to list the kernels RCCL itself launches, and
 with NCCL_DEBUG=INFO for RCCL's own init log (version, device, channels).
 
     python tools/diag_rccl.py          (prints one JSON line)
