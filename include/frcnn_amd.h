@@ -567,6 +567,25 @@ int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, c
                                     const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
                                     void* stream);
 
+/* The Double-Head regression branch's conv over RoI tiles (lib/heads/double_head.py:63-76,
+ * 119-122: Conv2d(cin, cout, 3, padding=1, bias=False), BatchNorm2d in eval mode, ReLU):
+ * y[i, co, p] = act((sum_ci sum_tap w[co, ci, tap] * x[i, ci, p + tap]) * s[co] + b[co]) over
+ * each RoI's 7 x 7 tile with zero padding 1 and stride 1, s and b as in frh_bn_act; the raw
+ * conv output is never written.  x [r, cin, 7, 7], y [r, cout, 7, 7] contiguous NCHW f32; w
+ * the Conv2d weight [cout, cin, 3, 3], contiguous; workspace:
+ * frh_roi_conv3x3_workspace(cin, cout) bytes (two launches: the weight repack into the
+ * workspace, which is redone on every call, then the convolution).  cin % 16 == 0,
+ * cout % 64 == 0, every pointer 16-byte aligned, y not overlapping x, w or the workspace
+ * (anything else: FRH_EINVAL); r == 0 launches nothing.  gamma / beta may be NULL (1 / 0);
+ * mean == var == NULL: no BN (the raw convolution, plus ReLU).  Each output is one exact-f32
+ * fmaf chain (f32 MFMA) in a fixed order with no atomics: a RoI's bits depend neither on r,
+ * nor on its index in the batch, nor on the launch, and given the same accumulator the
+ * epilogue gives frh_bn_act's bits. */
+size_t frh_roi_conv3x3_workspace(int32_t cin, int32_t cout);
+int32_t frh_roi_conv3x3_bn_act(const float* x, const float* w, float* y, const float* gamma, const float* beta,
+                               const float* mean, const float* var, float eps, int64_t r, int32_t cin,
+                               int32_t cout, int32_t relu, float* workspace, void* stream);
+
 /* FPN top-down merge into channels-last levels (lib/necks.py:72-84):
  * out[b, y, x, c] = (lat[b, c, y, x] + bias[c]) + up[b, iy, ix, c] with torch's nearest rule
  * (iy = min(floor(y * (float)up_h / height), up_h - 1); y / 2 when height == 2 * up_h);

@@ -1254,6 +1254,40 @@ def conv1x1_bn_act(conv, bn, x, skip=None, relu=True):
     return y
 
 
+def roi_conv3x3_fused_ok(conv, bn, x):
+    """Whether roi_conv3x3_bn_act takes the fused HIP entry for these arguments.  No RoI count is
+    excluded: tools/bench_roi_conv.py measured the entry faster than the modules at r = 512, 1000
+    and 2000 (both times in DESIGN section 4)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2:] == (7, 7) and x.is_contiguous()
+            and not bn.training and bn.running_mean is not None and conv.bias is None and conv.weight.dtype == torch.float32
+            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
+            and conv.weight.is_contiguous()):
+        return False
+    cout, cin = conv.out_channels, conv.in_channels
+    if x.shape[1] != cin or cin % 16 or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16:
+        return False
+    return not _needs_grad(x, conv.weight, bn.weight, bn.bias)
+
+
+def roi_conv3x3_bn_act(conv, bn, x, relu=True):
+    """act(bn(conv(x))) for the Double-Head regression branch's 3x3 / stride-1 / padding-1 conv over
+    the RoI tiles [R, cin, 7, 7] and its eval-mode BN in one fused launch pair
+    (frh_roi_conv3x3_bn_act: NCHW in and out, the BN / ReLU epilogue on the f32-MFMA accumulator)
+    when nothing needs a gradient through it (inference); otherwise the module ops, which covers
+    training-mode BN (batch statistics), any other stride or padding, and CPU tensors."""
+    if not roi_conv3x3_fused_ok(conv, bn, x):
+        y = bn(conv(x))
+        return torch.relu(y) if relu else y
+    r = x.shape[0]
+    y = torch.empty(r, conv.out_channels, 7, 7, dtype=torch.float32, device=x.device)
+    ws = torch.empty(9 * conv.in_channels * conv.out_channels, dtype=torch.float32, device=x.device)
+    call('frh_roi_conv3x3_bn_act', ptr(x), ptr(conv.weight), ptr(y), ptr(bn.weight), ptr(bn.bias),
+         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), r, conv.in_channels, conv.out_channels,
+         int(bool(relu)), ptr(ws), stream_of(x))
+    return y
+
+
 # Level sizes (h, w) at which tools/bench_conv3x3.py measured a frh_conv3x3_bias_act call of
 # that level alone slower than the MIOpen NHWC conv followed by its bias (+ ReLU) pass (too few
 # workgroups for the chip; both times in DESIGN section 4): alone they keep that path, in a
