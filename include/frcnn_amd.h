@@ -538,6 +538,43 @@ int32_t frh_conv1x1_bn_act(const float* x, const float* w, const float* skip, fl
                            const float* beta, const float* mean, const float* var, float eps, int64_t n,
                            int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream);
 
+/* frh_conv1x1_bn_act with the frozen BN (+ ReLU when pre_relu) that precedes the convolution
+ * (a bottleneck's bn2 in front of conv3) applied to x on its way into the GEMM: x is the raw
+ * output of the previous convolution, x' = act(x * s_in[ci] + b_in[ci]) with s_in / b_in from
+ * pre_gamma / pre_beta (may be NULL: 1 / 0) / pre_mean / pre_var / pre_eps as in frh_bn_act,
+ * then frh_conv1x1_bn_act on x'.  Same conditions, plus cin <= 512.  The result is bit for
+ * bit that of frh_bn_act followed by frh_conv1x1_bn_act; x' is never written. */
+int32_t frh_conv1x1_bn_act_pre(const float* x, const float* w, const float* skip, float* y, const float* gamma,
+                               const float* beta, const float* mean, const float* var, float eps,
+                               const float* pre_gamma, const float* pre_beta, const float* pre_mean,
+                               const float* pre_var, float pre_eps, int32_t pre_relu, int64_t n, int32_t cin,
+                               int32_t cout, int64_t hw, int32_t relu, void* stream);
+
+/* frh_conv1x1_bn_act for a 1x1 / stride-2 convolution (the bottleneck projections of stages 2
+ * to 4): x [n, cin, h, wd] contiguous NCHW is read at its even rows and columns,
+ * y / skip [n, cout, (h + 1) / 2, wd / 2].  wd % 8 == 0 (the output width a multiple of 4:
+ * anything else FRH_EINVAL), the other conditions as frh_conv1x1_bn_act.  The result is bit
+ * for bit that of frh_conv1x1_bn_act on a contiguous copy of x[:, :, ::2, ::2]. */
+int32_t frh_conv1x1_s2_bn_act(const float* x, const float* w, const float* skip, float* y, const float* gamma,
+                              const float* beta, const float* mean, const float* var, float eps, int64_t n,
+                              int32_t cin, int32_t cout, int32_t h, int32_t wd, int32_t relu, void* stream);
+
+/* The RPN head's classifier and regressor (lib/heads/rpn_head.py, RPNHead.forward: two 1x1
+ * convolutions on every level of the pyramid) in one launch: for num_levels (1..8) inputs
+ * xs[i] [n, level_hw[2i], level_hw[2i + 1], cin] f32 with channel stride 1 and element strides
+ * level_strides[3i..] = (image, row, column; non-negative multiples of 4),
+ * cls_outs[i][n, h, w, c_cls] = x . w_cls^T + b_cls and reg_outs[i][n, h, w, c_reg] =
+ * x . w_reg^T + b_reg, both contiguous channels-last; w_cls [c_cls, cin], w_reg [c_reg, cin]
+ * contiguous, the biases may be NULL.  cin % 8 == 0, cin <= 256, c_cls + c_reg <= 16, xs and
+ * the weights 16-byte aligned (anything else: FRH_EINVAL).  Every input element is read once
+ * and every output written once; each output is one exact-f32 fmaf chain (f32 MFMA) over cin
+ * in one fixed order, then + bias, with no atomics: the bits depend neither on the level, nor
+ * on the pixel, nor on what else is in the launch, nor on the launch. */
+int32_t frh_rpn_head1x1_levels(int32_t num_levels, const void* const* xs, void* const* cls_outs,
+                               void* const* reg_outs, const float* w_cls, const float* b_cls, const float* w_reg,
+                               const float* b_reg, int64_t n, int32_t cin, int32_t c_cls, int32_t c_reg,
+                               const int32_t* level_hw, const int64_t* level_strides, void* stream);
+
 /* The FPN output convs and the RPN head's shared conv (lib/necks.py, FPN.forward;
  * lib/heads/rpn_head.py, RPNHead.forward): y = act(conv3x3(x, w) + bias), padding 1, stride 1,
  * no dilation, no groups, as Winograd F(2x2, 3x3) on the f32 MFMA with the bias / ReLU

@@ -22,6 +22,17 @@
 // s and b of the tile's 64 channels are computed once per workgroup into LDS with
 // bn_act_kernel's expressions.  Workgroups are numbered cout-tile fastest and dealt to the 8
 // XCDs in contiguous chunks, so the cout tiles that re-read one X tile run on one L2.
+//
+// Two input-side forms of the same kernel (template flags; the plain instantiations compile
+// to what they were):
+//   PRE: the frozen BN (+ ReLU) that precedes the convolution (a bottleneck's bn2 in front of
+//     conv3) applied to the X registers between the global load and the LDS write, s_in / b_in
+//     of all cin channels computed once per workgroup into LDS with bn_act_kernel's
+//     expressions: the bits of frh_bn_act followed by the plain kernel, without that pass.
+//   S2: the X tile gathered from x[:, :, ::2, ::2] of an NCHW input (a stride-2 projection).
+//     With w_out % 4 == 0 a thread's four output pixels lie in one input row and are the
+//     .x / .z of two aligned float4 loads: the bits of the plain kernel on a contiguous copy
+//     of the subsampled input.
 #pragma once
 #include <math.h>
 
@@ -34,6 +45,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kCxThreads = 256;
 constexpr int kCxTile = 64;  // outputs per workgroup: kCxTile channels x kCxTile pixels
 constexpr int kCxXcds = 8;
+constexpr int kCxPreMax = 512;  // cin bound of the PRE form (s_in / b_in in LDS: 4 KB)
 
 struct Conv1x1Args {
   const float* x;
@@ -51,9 +63,25 @@ struct Conv1x1Args {
   int64_t total;  // mt * pt * n
   int64_t chunk;  // ceil(total / kCxXcds)
   int relu;
+  // PRE: the BN in front of the convolution (beta / gamma may be NULL)
+  const float* pre_gamma;
+  const float* pre_beta;
+  const float* pre_mean;
+  const float* pre_var;
+  float pre_eps;
+  int pre_relu;
+  // S2: the input plane (hw is the output plane, w_out its row length)
+  int64_t in_hw;
+  int in_w, w_out;
 };
 
-template <int BK>
+__device__ __forceinline__ float4 conv1x1_pre(float4 v, float s, float b, int relu) {
+  float4 r = make_float4(v.x * s + b, v.y * s + b, v.z * s + b, v.w * s + b);
+  if (relu) r = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), fmaxf(r.w, 0.0f));
+  return r;
+}
+
+template <int BK, bool PRE = false, bool S2 = false>
 __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x1Args a) {
   constexpr int T = kCxTile, PA = BK + 4, PB = T + 4, HK = BK / 2;
   constexpr int NV = T * (BK / 4) / kCxThreads;  // float4 of W, and of X, per thread per step
@@ -62,6 +90,7 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
   __shared__ __attribute__((aligned(16))) float As[2][T * PA];
   __shared__ __attribute__((aligned(16))) float Bs[2][BK * PB];
   __shared__ float bn_s[T], bn_b[T];
+  __shared__ float pre_s[PRE ? kCxPreMax : 1], pre_b[PRE ? kCxPreMax : 1];
 
   // XCD x takes logical workgroups [x * chunk, (x + 1) * chunk)
   const int64_t wg = (int64_t)(blockIdx.x % kCxXcds) * a.chunk + blockIdx.x / kCxXcds;
@@ -87,22 +116,44 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
     bn_b[tid] = (a.beta ? a.beta[c] : 0.0f) - a.mean[c] * s;
   }
 
+  if constexpr (PRE) {
+    for (int c = tid; c < a.cin; c += kCxThreads) {
+      const float s = (a.pre_gamma ? a.pre_gamma[c] : 1.0f) / sqrtf(a.pre_var[c] + a.pre_eps);
+      pre_s[c] = s;
+      pre_b[c] = (a.pre_beta ? a.pre_beta[c] : 0.0f) - a.pre_mean[c] * s;
+    }
+    __syncthreads();  // step 0 transforms its registers before the loop's first barrier
+  }
+
   // staging: thread t moves float4 t (and t + 256) of each tile; W rows are BK / 4 float4
-  // long, X rows 16.  Pixels past the plane's end stay zero (their columns are never stored).
+  // long, X rows 16.  Pixels past the plane's end stay zero (their columns are never stored,
+  // so what the PRE transform makes of those zeros does not matter).
   const int a_row = tid / (BK / 4), a_q = tid % (BK / 4);
   const int b_row = tid / (T / 4), b_q = tid % (T / 4);
   const float* wp = a.w + (int64_t)(m0 + a_row) * a.cin + a_q * 4;
   const bool p_ok = p0 + b_q * 4 < a.hw;
-  const float* xp = a.x + (img * a.cin + b_row) * a.hw + p0 + b_q * 4;
+  const float* xp;
+  if constexpr (S2) {
+    const int64_t pq = p0 + b_q * 4, oy = pq / a.w_out, ox = pq - oy * a.w_out;
+    xp = a.x + (img * a.cin + b_row) * a.in_hw + 2 * oy * a.in_w + 2 * ox;
+  } else {
+    xp = a.x + (img * a.cin + b_row) * a.hw + p0 + b_q * 4;
+  }
+  const int64_t xs = S2 ? a.in_hw : a.hw;  // X plane stride
   const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 ra0, ra1 = z4, rb0 = z4, rb1 = z4;
+  float4 rc0 = z4, rc1 = z4;  // S2: input columns 4 .. 7 of the thread's eight
 #define FRH_CX_LOAD(k0)                                                                         \
   do {                                                                                          \
     ra0 = *reinterpret_cast<const float4*>(wp + (k0));                                          \
     if (NV > 1) ra1 = *reinterpret_cast<const float4*>(wp + (int64_t)A_ROWS * a.cin + (k0));    \
     if (p_ok) {                                                                                 \
-      rb0 = *reinterpret_cast<const float4*>(xp + (int64_t)(k0)*a.hw);                          \
-      if (NV > 1) rb1 = *reinterpret_cast<const float4*>(xp + (int64_t)((k0) + B_ROWS) * a.hw); \
+      rb0 = *reinterpret_cast<const float4*>(xp + (int64_t)(k0)*xs);                            \
+      if (NV > 1) rb1 = *reinterpret_cast<const float4*>(xp + (int64_t)((k0) + B_ROWS) * xs);   \
+      if (S2) {                                                                                 \
+        rc0 = *reinterpret_cast<const float4*>(xp + (int64_t)(k0)*xs + 4);                      \
+        if (NV > 1) rc1 = *reinterpret_cast<const float4*>(xp + (int64_t)((k0) + B_ROWS) * xs + 4); \
+      }                                                                                         \
     }                                                                                           \
   } while (0)
 
@@ -117,8 +168,15 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
     // buffer buf was last read in step t - 2, which every wave left before the barrier of step t - 1
     *reinterpret_cast<float4*>(&As[buf][a_row * PA + a_q * 4]) = ra0;
     if (NV > 1) *reinterpret_cast<float4*>(&As[buf][(a_row + A_ROWS) * PA + a_q * 4]) = ra1;
-    *reinterpret_cast<float4*>(&Bs[buf][b_row * PB + b_q * 4]) = rb0;
-    if (NV > 1) *reinterpret_cast<float4*>(&Bs[buf][(b_row + B_ROWS) * PB + b_q * 4]) = rb1;
+    float4 vb0 = S2 ? make_float4(rb0.x, rb0.z, rc0.x, rc0.z) : rb0;
+    float4 vb1 = S2 ? make_float4(rb1.x, rb1.z, rc1.x, rc1.z) : rb1;
+    if constexpr (PRE) {
+      const int c = t * BK + b_row;
+      vb0 = conv1x1_pre(vb0, pre_s[c], pre_b[c], a.pre_relu);
+      if (NV > 1) vb1 = conv1x1_pre(vb1, pre_s[c + B_ROWS], pre_b[c + B_ROWS], a.pre_relu);
+    }
+    *reinterpret_cast<float4*>(&Bs[buf][b_row * PB + b_q * 4]) = vb0;
+    if (NV > 1) *reinterpret_cast<float4*>(&Bs[buf][(b_row + B_ROWS) * PB + b_q * 4]) = vb1;
     __syncthreads();
     if (t + 1 < steps) FRH_CX_LOAD((t + 1) * BK);  // in flight behind this step's MFMAs
 #pragma unroll
@@ -162,9 +220,23 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
 // tools/bench_conv1x1.py.
 inline int conv1x1_pick_step(int32_t cin) { return cin >= 128 && cin % 32 == 0 ? 32 : 16; }
 
+// The input-side forms: pre != NULL is PRE (its mean / var given), in_w > 0 is S2 (x is
+// [n, cin, in_h, in_w], hw the output plane ((in_h + 1) / 2) * (in_w / 2)); not both.
+struct Conv1x1Input {
+  const float* pre_gamma = nullptr;
+  const float* pre_beta = nullptr;
+  const float* pre_mean = nullptr;
+  const float* pre_var = nullptr;
+  float pre_eps = 0.0f;
+  int32_t pre_relu = 0;
+  int32_t in_h = 0, in_w = 0;
+};
+
 inline int32_t conv1x1_launch(int step, const float* x, const float* w, const float* skip, float* y,
                               const float* gamma, const float* beta, const float* mean, const float* var, float eps,
-                              int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream) {
+                              int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream,
+                              const Conv1x1Input* in = nullptr, const char* what = "frh_conv1x1_bn_act") {
+  const bool pre = in && in->pre_mean, s2 = in && in->in_w > 0;
   FRH_REQUIRE(n >= 0 && cin >= 1 && cout >= 1 && hw >= 0, "bad sizes");
   if (n == 0 || hw == 0) return FRH_OK;
   FRH_REQUIRE(x && w && y, "null pointer argument");
@@ -175,7 +247,22 @@ inline int32_t conv1x1_launch(int step, const float* x, const float* w, const fl
               "tensors must be 16-byte aligned");
   FRH_REQUIRE(y != x && y != skip, "y must not alias x or skip");
   FRH_REQUIRE((step == 16 || step == 32) && cin % step == 0, "step %d does not fit cin %d", step, cin);
+  FRH_REQUIRE(!(pre && s2), "the input BN and the stride-2 gather are separate forms");
   Conv1x1Args a;
+  a.pre_gamma = a.pre_beta = a.pre_mean = a.pre_var = nullptr, a.pre_eps = 0.0f, a.pre_relu = 0;
+  a.in_hw = 0, a.in_w = a.w_out = 0;
+  if (in && !s2) {
+    FRH_REQUIRE(in->pre_mean && in->pre_var, "the input BN needs its mean and var");
+    FRH_REQUIRE(cin <= kCxPreMax, "cin %d above the input BN form's bound %d", cin, kCxPreMax);
+    a.pre_gamma = in->pre_gamma, a.pre_beta = in->pre_beta, a.pre_mean = in->pre_mean, a.pre_var = in->pre_var;
+    a.pre_eps = in->pre_eps, a.pre_relu = in->pre_relu;
+  }
+  if (s2) {
+    FRH_REQUIRE(in->in_h >= 1 && in->in_w % 8 == 0,
+                "input width %d must be a multiple of 8 (output width a multiple of 4)", in->in_w);
+    FRH_REQUIRE(hw == (int64_t)((in->in_h + 1) / 2) * (in->in_w / 2), "output plane does not match the input");
+    a.in_hw = (int64_t)in->in_h * in->in_w, a.in_w = in->in_w, a.w_out = in->in_w / 2;
+  }
   a.x = x, a.w = w, a.skip = skip, a.y = y, a.gamma = gamma, a.beta = beta, a.mean = mean, a.var = var, a.eps = eps;
   a.cin = cin, a.cout = cout, a.hw = hw, a.relu = relu;
   a.mt = cout / kCxTile;
@@ -186,11 +273,21 @@ inline int32_t conv1x1_launch(int step, const float* x, const float* w, const fl
   a.chunk = (a.total + kCxXcds - 1) / kCxXcds;
   FRH_REQUIRE(a.chunk * kCxXcds < ((int64_t)1 << 31), "too many blocks");
   const dim3 grid((unsigned)(a.chunk * kCxXcds)), block(kCxThreads);
-  if (step == 32)
-    hipLaunchKernelGGL((conv1x1_bn_act_kernel<32>), grid, block, 0, as_stream(stream), a);
+#define FRH_CX_GO(PRE, S2)                                                                             \
+  do {                                                                                                 \
+    if (step == 32)                                                                                    \
+      hipLaunchKernelGGL((conv1x1_bn_act_kernel<32, PRE, S2>), grid, block, 0, as_stream(stream), a);  \
+    else                                                                                               \
+      hipLaunchKernelGGL((conv1x1_bn_act_kernel<16, PRE, S2>), grid, block, 0, as_stream(stream), a);  \
+  } while (0)
+  if (pre)
+    FRH_CX_GO(true, false);
+  else if (s2)
+    FRH_CX_GO(false, true);
   else
-    hipLaunchKernelGGL((conv1x1_bn_act_kernel<16>), grid, block, 0, as_stream(stream), a);
-  return check_launch("frh_conv1x1_bn_act");
+    FRH_CX_GO(false, false);
+#undef FRH_CX_GO
+  return check_launch(what);
 }
 
 }  // namespace frh

@@ -103,6 +103,12 @@ SIGNATURES = {
     'frh_bn_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i64, c_i32, c_vp]),
     'frh_conv1x1_bn_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_i64, c_i32,
                                    c_vp]),
+    'frh_conv1x1_bn_act_pre': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp,
+                                       c_f32, c_i32, c_i64, c_i32, c_i32, c_i64, c_i32, c_vp]),
+    'frh_conv1x1_s2_bn_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32,
+                                      c_i32, c_i32, c_i32, c_vp]),
+    'frh_rpn_head1x1_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), P(c_vp), c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
+                                       c_i32, P(c_i32), P(c_i64), c_vp]),
     'frh_conv3x3_workspace': (c_size, [c_i32, c_i32]),
     'frh_conv3x3_bias_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
                                      c_i32, c_vp]),

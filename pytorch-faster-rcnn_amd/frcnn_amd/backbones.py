@@ -16,7 +16,7 @@ import logging
 import torch
 from torch import nn
 
-from .ops import bn_act, bn_act_maxpool, conv1x1_bn_act
+from .ops import bn_act_maxpool, conv1x1_bn_act, conv1x1_s2_bn_act
 
 # blocks per stage for each depth
 _STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -45,12 +45,16 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         # frozen BN (+ residual) + ReLU: inside the 1x1 convs' HIP GEMM where nothing needs a
-        # gradient (ops.conv1x1_bn_act; the stride-2 projections and every training path fall
-        # through to conv + ops.bn_act), one HIP epilogue pass after the 3x3 conv (ops.bn_act)
+        # gradient (ops.conv1x1_bn_act, ops.conv1x1_s2_bn_act for the stride-2 projections; every
+        # training path falls through to conv + ops.bn_act).  The 3x3 conv's BN + ReLU is applied
+        # on conv3's input side (pre_bn), or by one HIP epilogue pass (ops.bn_act) where it cannot.
         y = conv1x1_bn_act(self.conv1, self.bn1, x)
-        y = bn_act(self.conv2(y), self.bn2)
-        skip = conv1x1_bn_act(self.downsample[0], self.downsample[1], x, relu=False) if self.do_downsample else x
-        return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip)
+        y = self.conv2(y)
+        skip = x
+        if self.do_downsample:
+            proj = conv1x1_s2_bn_act if self.downsample[0].stride == (2, 2) else conv1x1_bn_act
+            skip = proj(self.downsample[0], self.downsample[1], x, relu=False)
+        return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip, pre_bn=self.bn2)
 
 
 class ResNet(nn.Module):

@@ -1,6 +1,7 @@
 """RPNHead (reference lib/heads/rpn_head.py).
 
-Convs stay on PyTorch-ROCm.  `predict_bboxes_from_output` runs the whole
+Where nothing needs a gradient the convs run in this library (`ops.conv3x3_bias_act_levels`,
+`ops.rpn_head1x1_levels`); otherwise on PyTorch-ROCm.  `predict_bboxes_from_output` runs the whole
 proposal stage (rpn_head.py:68-120: per-level score top-k, decode + clamp,
 min-size filter, NMS, post_nms cut, cross-level top-k) for every image and
 level in one `frh_rpn_proposals` call, with no host synchronisation: the
@@ -81,7 +82,8 @@ class RPNHead(AnchorHead):
         # otherwise per level, the bias add + ReLU one pass on channels-last HIP levels
         # (ops.conv_bias_relu)
         hidden = ops.conv3x3_bias_act_levels(self.conv, xs, relu=True)
-        return [self.classifier(h) for h in hidden], [self.regressor(h) for h in hidden]
+        # classifier and regressor: one launch over every level where nothing needs a gradient
+        return ops.rpn_head1x1_levels(self.classifier, self.regressor, hidden)
 
     def predict_bboxes_from_output(self, cls_outs, reg_outs, img_metas, test_cfg):
         """Returns [props, scores, labels] lists like unpack_multi_result of

@@ -1239,19 +1239,147 @@ def conv1x1_fused_ok(conv, bn, x, skip=None):
     return not _needs_grad(x, skip, conv.weight, bn.weight, bn.bias)
 
 
-def conv1x1_bn_act(conv, bn, x, skip=None, relu=True):
+# Channel classes (cin, cout) at which tools/bench_conv1x1.py measured frh_conv1x1_bn_act_pre /
+# frh_conv1x1_s2_bn_act slower than what they replace (both times in DESIGN section 4).
+_CONV1X1_PRE_EXCLUDED = frozenset([(512, 2048)])
+_CONV1X1_S2_EXCLUDED = frozenset([(512, 1024), (1024, 2048)])
+_CONV1X1_PRE_MAX_CIN = 512
+
+
+def conv1x1_pre_fused_ok(conv, bn, x, pre_bn, skip=None):
+    """Whether conv1x1_bn_act folds pre_bn (+ ReLU) into the fused entry's input side."""
+    return (conv1x1_fused_ok(conv, bn, x, skip) and not pre_bn.training and pre_bn.running_mean is not None
+            and pre_bn.num_features == conv.in_channels and conv.in_channels <= _CONV1X1_PRE_MAX_CIN
+            and (conv.in_channels, conv.out_channels) not in _CONV1X1_PRE_EXCLUDED
+            and not _needs_grad(pre_bn.weight, pre_bn.bias))
+
+
+def conv1x1_bn_act(conv, bn, x, skip=None, relu=True, pre_bn=None):
     """act(bn(conv(x)) (+ skip)) for a bottleneck's 1x1 / stride-1 conv and its eval-mode BN in
     one HIP launch (frh_conv1x1_bn_act: the BN / residual / ReLU epilogue on the GEMM's
     accumulator, no raw conv output in HBM) when nothing needs a gradient through it (the graphed
-    trunk, inference, frozen stages); otherwise bn_act(conv(x), bn, skip, relu)."""
+    trunk, inference, frozen stages); otherwise bn_act(conv(x), bn, skip, relu).
+    pre_bn: x is the raw output of the previous conv and relu(pre_bn(x)) is what this conv reads;
+    where the fused conditions hold that BN + ReLU is applied inside the same launch
+    (frh_conv1x1_bn_act_pre), otherwise by ops.bn_act first."""
+    if pre_bn is not None and not conv1x1_pre_fused_ok(conv, bn, x, pre_bn, skip):
+        x, pre_bn = bn_act(x, pre_bn), None
     if not conv1x1_fused_ok(conv, bn, x, skip):
         return bn_act(conv(x), bn, skip=skip, relu=relu)
     n, _, h, w = x.shape
     y = torch.empty(n, conv.out_channels, h, w, dtype=torch.float32, device=x.device)
+    if pre_bn is not None:
+        call('frh_conv1x1_bn_act_pre', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), ptr(bn.weight), ptr(bn.bias),
+             ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(pre_bn.weight), ptr(pre_bn.bias),
+             ptr(pre_bn.running_mean), ptr(pre_bn.running_var), float(pre_bn.eps), 1, n, conv.in_channels,
+             conv.out_channels, h * w, int(bool(relu)), stream_of(x))
+        return y
     call('frh_conv1x1_bn_act', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), ptr(bn.weight), ptr(bn.bias),
          ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), n, conv.in_channels, conv.out_channels, h * w,
          int(bool(relu)), stream_of(x))
     return y
+
+
+def conv1x1_s2_fused_ok(conv, bn, x):
+    """Whether conv1x1_s2_bn_act takes the fused HIP entry for these arguments."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+            and not bn.training and bn.running_mean is not None and conv.bias is None
+            and conv.weight.dtype == torch.float32 and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
+            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.weight.is_contiguous()):
+        return False
+    cout, cin = conv.out_channels, conv.in_channels
+    if x.shape[1] != cin or x.shape[0] == 0 or x.shape[2] == 0 or x.shape[3] == 0 or x.shape[3] % 8 or cin % 16 \
+            or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16 or (cin, cout) in _CONV1X1_S2_EXCLUDED:
+        return False
+    return not _needs_grad(x, conv.weight, bn.weight, bn.bias)
+
+
+def conv1x1_s2_bn_act(conv, bn, x, relu=False):
+    """act(bn(conv(x))) for a bottleneck's 1x1 / stride-2 projection and its eval-mode BN in one
+    HIP launch (frh_conv1x1_s2_bn_act: the GEMM of conv1x1_bn_act reading x at its even rows and
+    columns, output width a multiple of 4) when nothing needs a gradient through it; otherwise
+    bn_act(conv(x), bn, relu=relu)."""
+    if not conv1x1_s2_fused_ok(conv, bn, x):
+        return bn_act(conv(x), bn, relu=relu)
+    n, _, h, w = x.shape
+    y = torch.empty(n, conv.out_channels, (h + 1) // 2, w // 2, dtype=torch.float32, device=x.device)
+    call('frh_conv1x1_s2_bn_act', ptr(x), ptr(conv.weight), None, ptr(y), ptr(bn.weight), ptr(bn.bias),
+         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), n, conv.in_channels, conv.out_channels, h, w,
+         int(bool(relu)), stream_of(x))
+    return y
+
+
+_RPN_HEAD1X1_MAX_COUT = 16
+_RPN_HEAD1X1_MAX_CIN = 256
+
+
+def _plain_1x1(conv):
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.weight.dtype == torch.float32
+            and conv.weight.stride(0) == conv.in_channels and conv.weight.stride(1) == 1
+            and conv.weight.data_ptr() % 16 == 0
+            and (conv.bias is None or (conv.bias.dtype == torch.float32 and conv.bias.is_contiguous())))
+
+
+def rpn_head1x1_fused_ok(classifier, regressor, hidden):
+    """Whether rpn_head1x1_levels takes the fused HIP entry for these arguments."""
+    hidden = list(hidden)
+    if not hidden or len(hidden) > 8 or not (_plain_1x1(classifier) and _plain_1x1(regressor)):
+        return False
+    cin = classifier.in_channels
+    if regressor.in_channels != cin or cin % 8 or cin > _RPN_HEAD1X1_MAX_CIN \
+            or classifier.out_channels + regressor.out_channels > _RPN_HEAD1X1_MAX_COUT:
+        return False
+    x0 = hidden[0]
+    for x in hidden:
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.device == x0.device
+                and x.shape[0] == x0.shape[0] and x.shape[1] == cin and x.numel() > 0 and x.stride(1) == 1
+                and (x.shape[2] * x.shape[3] == 1 or _suggests_channels_last(x))
+                and x.data_ptr() % 16 == 0 and all(s >= 0 and s % 4 == 0 for i, (d, s) in enumerate(zip(x.shape, x.stride())) if i != 1 and d > 1)
+                and x.shape[0] * x.shape[2] * x.shape[3] < 1 << 31):
+            return False
+    return not _needs_grad(classifier.weight, classifier.bias, regressor.weight, regressor.bias, *hidden)
+
+
+def _suggests_channels_last(t):
+    """torch's own stride rule (c10 is_channels_last_strides_4d) for whether a conv returns a
+    channels-last output for this 4-d input or weight."""
+    least = 0
+    if t.stride(1) == 0:
+        return False
+    for d in (1, 3, 2, 0):
+        if t.shape[d] == 0 or t.stride(d) < least or (d == 0 and least == t.stride(1)):
+            return False
+        least = t.stride(d) * max(t.shape[d], 1)
+    return True
+
+
+def rpn_head1x1_levels(classifier, regressor, hidden):
+    """([classifier(h) for h in hidden], [regressor(h) for h in hidden]) for the RPN head's two
+    1x1 convs: one HIP launch over every level (frh_rpn_head1x1_levels: each level read once for
+    both convs, bias on the accumulator, one fixed-order f32 sum per output) on channels-last f32
+    HIP levels when nothing needs a gradient; otherwise the module calls.  The outputs are
+    channels-last, as the modules return for a channels-last input."""
+    hidden = list(hidden)
+    if not rpn_head1x1_fused_ok(classifier, regressor, hidden):
+        return [classifier(h) for h in hidden], [regressor(h) for h in hidden]
+    n, dev, cin = hidden[0].shape[0], hidden[0].device, classifier.in_channels
+    cc, cr = classifier.out_channels, regressor.out_channels
+    def out(conv, x):
+        # the memory is [n, h, w, c] either way; a one-pixel level is also NCHW-contiguous, and
+        # then the modules return it with those strides
+        fmt = torch.channels_last if _suggests_channels_last(x) or _suggests_channels_last(conv.weight) \
+            else torch.contiguous_format
+        return torch.empty((n, conv.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32, device=dev,
+                           memory_format=fmt)
+    cls = [out(classifier, x) for x in hidden]
+    reg = [out(regressor, x) for x in hidden]
+    call('frh_rpn_head1x1_levels', len(hidden), ptr_array(hidden), ptr_array(cls), ptr_array(reg),
+         ptr(classifier.weight), ptr(classifier.bias), ptr(regressor.weight), ptr(regressor.bias), n, cin, cc, cr,
+         i32_array([v for x in hidden for v in x.shape[2:]]),
+         i64_array([v for x in hidden for v in (x.stride(0), x.stride(2), x.stride(3))]), stream_of(hidden[0]))
+    return cls, reg
 
 
 def roi_conv3x3_fused_ok(conv, bn, x):

@@ -14,7 +14,18 @@ tensors so a call does not find its own output in the caches.
 Per shape it prints us for both paths, FLOPs, algorithmic bytes of the fused op (x, w, skip
 read once, y written once) and the share of the binding limit the fused kernel reaches,
 the limit being the larger of FLOPs / 157.3 TFLOP/s and bytes / 8 TB/s.  The weighted sums
-are the per-step totals of the 33 launches."""
+are the per-step totals of the 33 launches.
+
+    python tools/bench_conv1x1.py --mode pre [--out profiles/small_passes/bench_conv1x1_pre.json]
+    python tools/bench_conv1x1.py --mode s2  [--out profiles/small_passes/bench_conv1x1_s2.json]
+
+time the input-side forms of the same kernel against what they replace, 20 calls between the
+event pair, 7 repetitions with the sides alternating, median with [min, max]; a side wins only
+when its slowest repetition beats the other side's fastest:
+  pre: the four conv3 classes; parent = frh_bn_act (bn2 + ReLU on conv2's raw output) then
+       frh_conv1x1_bn_act; new = frh_conv1x1_bn_act_pre on the raw output.
+  s2:  the three stride-2 projections; parent = F.conv2d stride 2 (MIOpen's search warmed) then
+       frh_bn_act; new = frh_conv1x1_s2_bn_act."""
 import argparse
 import json
 import os
@@ -46,6 +57,10 @@ SHAPES = [
     (2048, 512, 608, 2, False, True, 'stage 4 conv1'),
     (512, 2048, 608, 3, True, True, 'stage 4 conv3'),
 ]
+# conv3 (cin, cout, hw, launches per step): every one has the skip and the ReLU
+PRE_SHAPES = [(64, 256, 38912, 3), (128, 512, 9728, 4), (256, 1024, 2432, 6), (512, 2048, 608, 3)]
+# the stride-2 projections (cin, cout, input h, input w), one per step each
+S2_SHAPES = [(256, 512, 152, 256), (512, 1024, 76, 128), (1024, 2048, 38, 64)]
 PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
 SETS = 3
 
@@ -62,13 +77,108 @@ def time_calls(fns, iters):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
+def _bn(c, dev):
+    bn = torch.nn.BatchNorm2d(c).to(dev).eval()
+    bn.running_var.uniform_(0.5, 2.0)
+    bn.running_mean.uniform_(-1, 1)
+    return bn
+
+
+def _bn_ptrs(bn):
+    from frcnn_amd import _lib
+    return (_lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps))
+
+
+def input_forms(mode, out, iters=20, reps=7):
+    """--mode pre / s2: the input-side forms against the launches they replace."""
+    from frcnn_amd import _lib, ops
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    p = _lib.ptr
+    rows = []
+    with torch.no_grad():
+        for shape in (PRE_SHAPES if mode == 'pre' else S2_SHAPES):
+            if mode == 'pre':
+                cin, cout, hw, count = shape
+                h, w, oh, ow = hw // 32, 32, hw // 32, 32
+                stride = 1
+            else:
+                cin, cout, h, w = shape
+                count, oh, ow, stride = 1, (h + 1) // 2, w // 2, 2
+            conv = torch.nn.Conv2d(cin, cout, 1, stride=stride, bias=False).to(dev)
+            bn, pre = _bn(cout, dev), _bn(cin, dev)
+            xs = [torch.randn(N, cin, h, w, device=dev) for _ in range(SETS)]
+            mids = [torch.empty(N, cin, h, w, device=dev) for _ in range(SETS)]
+            sk = [torch.randn(N, cout, oh, ow, device=dev) if mode == 'pre' else None for _ in range(SETS)]
+            ys = [torch.empty(N, cout, oh, ow, device=dev) for _ in range(SETS)]
+            yp = [torch.empty(N, cout, oh, ow, device=dev) for _ in range(SETS)]
+            st = _lib.stream_of(xs[0])
+
+            def parent(i):
+                if mode == 'pre':
+                    def run():
+                        _lib.call('frh_bn_act', p(xs[i]), None, p(mids[i]), *_bn_ptrs(pre), N, cin, h * w, 1, st)
+                        _lib.call('frh_conv1x1_bn_act', p(mids[i]), p(conv.weight), p(sk[i]), p(yp[i]), *_bn_ptrs(bn), N,
+                                  cin, cout, h * w, 1, st)
+                    return run
+
+                def run():
+                    raw = F.conv2d(xs[i], conv.weight, stride=2)
+                    _lib.call('frh_bn_act', p(raw), None, p(yp[i]), *_bn_ptrs(bn), N, cout, oh * ow, 0, st)
+                return run
+
+            def new(i):
+                if mode == 'pre':
+                    return lambda: _lib.call('frh_conv1x1_bn_act_pre', p(xs[i]), p(conv.weight), p(sk[i]), p(ys[i]),
+                                             *_bn_ptrs(bn), *_bn_ptrs(pre), 1, N, cin, cout, h * w, 1, st)
+                return lambda: _lib.call('frh_conv1x1_s2_bn_act', p(xs[i]), p(conv.weight), None, p(ys[i]),
+                                         *_bn_ptrs(bn), N, cin, cout, h, w, 0, st)
+            sides = {'parent': [parent(i) for i in range(SETS)], 'new': [new(i) for i in range(SETS)]}
+            for fns in sides.values():
+                for f in fns:
+                    f()
+                    f()
+            torch.cuda.synchronize()
+            maxdiff = float((yp[0] - ys[0]).abs().max() / yp[0].abs().max())
+            t = {k: [] for k in sides}
+            for _ in range(reps):
+                for k, fns in sides.items():
+                    t[k].append(time_calls(fns, iters))
+            stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
+            row = {'cin': cin, 'cout': cout, 'input_hw': [h, w], 'launches_per_step': count,
+                   'max_rel_diff_vs_parent': maxdiff, 'new_wins': stat['new'][2] < stat['parent'][1],
+                   'parent_wins': stat['parent'][2] < stat['new'][1]}
+            for k, (med, lo, hi) in stat.items():
+                row[k + '_us'] = round(med, 1)
+                row[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
+            rows.append(row)
+            print('{} {:5d}->{:4d} @ {}x{} x{}  parent {:7.1f} us [{:.1f}, {:.1f}]  new {:7.1f} us [{:.1f}, {:.1f}]  '
+                  'new wins {}  diff {:.1e}'.format(mode, cin, cout, h, w, count, *stat['parent'], *stat['new'],
+                                                   row['new_wins'], maxdiff), flush=True)
+            del xs, mids, sk, ys, yp
+    res = {'device': torch.cuda.get_device_name(0), 'mode': mode, 'iters': iters, 'reps': reps, 'batch': N,
+           'shapes': rows,
+           'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
+           'per_step_new_us': round(sum(r['new_us'] * r['launches_per_step'] for r in rows), 1)}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k != 'shapes'}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'conv1x1', 'bench_conv1x1.json'))
+    ap.add_argument('--mode', default='stride1', choices=['stride1', 'pre', 's2'])
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_conv1x1 needs a HIP device')
+    if args.mode != 'stride1':
+        return input_forms(args.mode, args.out or os.path.join(REPO, 'profiles', 'small_passes',
+                                                               'bench_conv1x1_{}.json'.format(args.mode)))
+    args.out = args.out or os.path.join(REPO, 'profiles', 'conv1x1', 'bench_conv1x1.json')
     from frcnn_amd import _lib, ops
     try:
         import toolslib

@@ -19,6 +19,7 @@ CLASSES = [
     ('RoIAlign backward', ('roi_align_bwd',)),
     ('NMS', ('nms_',)),
     ('segmented top-k (+ fused sort/decode, label apply)', ('tk_', 'rpn_select', 'sampler_select')),
+    ('RPN head 1x1 convs, all levels', ('rpn_head1x1',)),
     ('RPN select/decode/merge', ('rpn_',)),
     ('assignment', ('assign_',)),
     ('sampler compaction', ('chunk_',)),
