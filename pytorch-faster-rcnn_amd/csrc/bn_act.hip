@@ -4,11 +4,9 @@
 // each BN is a per-channel affine map of its conv's output; PyTorch runs it as three
 // kernels (BN, add, clamp) with a full read + write of the activation each.  Here one
 // workgroup row handles one (image, channel) plane: s and b are computed once per block
-// from the BN parameters (no host-side folding, so trainable gamma/beta stay live), and
-// the plane streams through float4 loads/stores.  In place (y == x) is allowed.
-#include <math.h>
-
-#include "common.h"
+// from the BN parameters (bn_fold.h holds the arithmetic), and the plane streams through float4
+// loads/stores.  In place (y == x) is allowed.
+#include "bn_fold.h"
 
 namespace frh {
 
@@ -24,8 +22,8 @@ __global__ void __launch_bounds__(kBnThreads) bn_act_kernel(const float4* x, con
   const int64_t plane = blockIdx.x / tiles;
   const int tile = blockIdx.x - (int)(plane * tiles);
   const int c = (int)(plane % C);
-  const float s = (gamma ? gamma[c] : 1.0f) / sqrtf(var[c] + eps);
-  const float b = (beta ? beta[c] : 0.0f) - mean[c] * s;
+  float s, b;
+  bn_fold({gamma, beta, mean, var, eps}, c, s, b);
   const int64_t base = plane * hw4;
   for (int64_t i0 = (int64_t)tile * kBnThreads * kBnVec + threadIdx.x; i0 < hw4;
        i0 += (int64_t)tiles * kBnThreads * kBnVec) {
@@ -41,12 +39,7 @@ __global__ void __launch_bounds__(kBnThreads) bn_act_kernel(const float4* x, con
 #pragma unroll
     for (int u = 0; u < kBnVec; ++u) {
       const int64_t i = i0 + u * kBnThreads;
-      if (i < hw4) {
-        float4 r = make_float4(v[u].x * s + b, v[u].y * s + b, v[u].z * s + b, v[u].w * s + b);
-        if (skip) r = make_float4(r.x + k[u].x, r.y + k[u].y, r.z + k[u].z, r.w + k[u].w);
-        if (relu) r = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), fmaxf(r.w, 0.0f));
-        y[base + i] = r;
-      }
+      if (i < hw4) y[base + i] = bn_apply(v[u], true, &s, &b, skip != nullptr, &k[u], relu);
     }
   }
 }
@@ -62,7 +55,7 @@ extern "C" int32_t frh_bn_act(const float* x, const float* skip, float* y, const
   if (n == 0 || hw == 0) return FRH_OK;
   FRH_REQUIRE(x && y && mean && var, "null pointer argument");
   FRH_REQUIRE(hw % 4 == 0, "plane size %lld must be a multiple of 4", (long long)hw);
-  FRH_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)skip) % 16 == 0, "tensors must be 16-byte aligned");
+  FRH_REQUIRE_ALIGNED16(x, y, skip);
   const int64_t hw4 = hw / 4;
   const int64_t per_block = (int64_t)kBnThreads * kBnVec;
   const int64_t tiles = (hw4 + per_block - 1) / per_block;
@@ -78,8 +71,8 @@ extern "C" int32_t frh_bn_act(const float* x, const float* skip, float* y, const
 // the pooled map is written (PyTorch: BN-act pass + max_pool2d_with_indices, which also
 // writes int64 indices).  Thread = four consecutive outputs of one row: input columns
 // 8q - 1 .. 8q + 7 of the (up to) three input rows, as two float4 + one scalar each.
-// Max over the window's in-bounds elements (the pool's -inf padding); same f32 BN
-// arithmetic as bn_act_kernel, so every output equals max_pool2d(bn_act(x)) bit for bit.
+// Max over the window's in-bounds elements (the pool's -inf padding); the BN arithmetic is
+// bn_fold.h's, so every output equals max_pool2d(bn_act(x)) bit for bit.
 namespace frh {
 
 __global__ void __launch_bounds__(kBnThreads) bn_act_maxpool_kernel(const float* __restrict__ x, float4* y,
@@ -96,9 +89,9 @@ __global__ void __launch_bounds__(kBnThreads) bn_act_maxpool_kernel(const float*
   const int oy = (int)(r % OH);
   const int64_t plane = r / OH;
   const int c = (int)(plane % C);
-  const float s = (gamma ? gamma[c] : 1.0f) / sqrtf(var[c] + eps);
-  const float b = (beta ? beta[c] : 0.0f) - mean[c] * s;
-  auto act = [&](float v) { return fmaxf(v * s + b, 0.0f); };
+  float s, b;
+  bn_fold({gamma, beta, mean, var, eps}, c, s, b);
+  auto act = [&](float v) { return bn_apply(v, true, &s, &b, false, nullptr, true); };
   float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
   const float* xp = x + plane * (int64_t)H * W;
 #pragma unroll
@@ -128,7 +121,7 @@ extern "C" int32_t frh_bn_act_maxpool(const float* x, float* y, const float* gam
   if (n == 0) return FRH_OK;
   FRH_REQUIRE(x && y && mean && var, "null pointer argument");
   FRH_REQUIRE(w % 8 == 0, "width %d must be a multiple of 8", w);
-  FRH_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "tensors must be 16-byte aligned");
+  FRH_REQUIRE_ALIGNED16(x, y);
   const int oh = (h - 1) / 2 + 1;
   const int64_t total = n * (int64_t)c * oh * (w / 8);
   const int64_t blocks = (total + kBnThreads - 1) / kBnThreads;

@@ -34,6 +34,19 @@ int32_t check_launch(const char* what);
     }                                                                   \
   } while (0)
 
+// The host checks the fused entries share.
+template <class... P>
+inline bool aligned16(const P*... p) {
+  return (((uintptr_t)p | ...) & 15) == 0;  // a NULL (optional) pointer passes
+}
+#define FRH_REQUIRE_ALIGNED16(...) FRH_REQUIRE(::frh::aligned16(__VA_ARGS__), "tensors must be 16-byte aligned")
+
+// whether the byte ranges [p, p + pn) and [q, q + qn) share a byte
+inline bool ranges_overlap(const void* p, int64_t pn, const void* q, int64_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + (uintptr_t)qn && b < a + (uintptr_t)pn;
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Workgroups of `kernel` (block threads, dynamic LDS bytes) the current device holds at
@@ -44,6 +57,14 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 int resident_capacity(const void* kernel, int block, size_t dyn_lds = 0);
 
 constexpr int kWave = 64;
+
+// ---------------------------------------------------------------- MFMA
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// v_mfma_f32_32x32: accumulator register r (0 .. 15) of lane (h = lane >> 5, j = lane & 31) is
+// the tile's row mfma32_row(r) + 4 h, column j.
+__device__ __forceinline__ constexpr int mfma32_row(int r) { return (r & 3) + 8 * (r >> 2); }
 
 // ---------------------------------------------------------------- box math
 // calc_iou (reference lib/utils.py:151-172): +1 widths, intersection zeroed

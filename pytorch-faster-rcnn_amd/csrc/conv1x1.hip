@@ -8,8 +8,8 @@ using namespace frh;
 extern "C" int32_t frh_conv1x1_bn_act(const float* x, const float* w, const float* skip, float* y, const float* gamma,
                                       const float* beta, const float* mean, const float* var, float eps, int64_t n,
                                       int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream) {
-  return conv1x1_launch(conv1x1_pick_step(cin), x, w, skip, y, gamma, beta, mean, var, eps, n, cin, cout, hw, relu,
-                        stream);
+  return conv1x1_launch("frh_conv1x1_bn_act", conv1x1_pick_step(cin), x, w, skip, y, {gamma, beta, mean, var, eps}, n,
+                        cin, cout, hw, relu, stream);
 }
 
 // frh_conv1x1_bn_act_pre: the same kernel with the BN (+ ReLU) that precedes the convolution
@@ -22,11 +22,9 @@ extern "C" int32_t frh_conv1x1_bn_act_pre(const float* x, const float* w, const 
                                           int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu,
                                           void* stream) {
   FRH_REQUIRE(pre_mean && pre_var, "the input BN needs its mean and var");
-  Conv1x1Input in;
-  in.pre_gamma = pre_gamma, in.pre_beta = pre_beta, in.pre_mean = pre_mean, in.pre_var = pre_var;
-  in.pre_eps = pre_eps, in.pre_relu = pre_relu;
-  return conv1x1_launch(conv1x1_pick_step(cin), x, w, skip, y, gamma, beta, mean, var, eps, n, cin, cout, hw, relu,
-                        stream, &in, "frh_conv1x1_bn_act_pre");
+  return conv1x1_launch("frh_conv1x1_bn_act_pre", conv1x1_pick_step(cin), x, w, skip, y,
+                        {gamma, beta, mean, var, eps}, n, cin, cout, hw, relu, stream,
+                        {pre_gamma, pre_beta, pre_mean, pre_var, pre_eps}, pre_relu);
 }
 
 // frh_conv1x1_s2_bn_act: the same kernel with its X tile gathered from x[:, :, ::2, ::2] (the
@@ -37,8 +35,7 @@ extern "C" int32_t frh_conv1x1_s2_bn_act(const float* x, const float* w, const f
                                          int32_t relu, void* stream) {
   FRH_REQUIRE(h >= 1 && wd >= 1, "bad sizes");
   FRH_REQUIRE(wd % 8 == 0, "input width %d must be a multiple of 8 (output width a multiple of 4)", wd);
-  Conv1x1Input in;
-  in.in_h = h, in.in_w = wd;
-  return conv1x1_launch(conv1x1_pick_step(cin), x, w, skip, y, gamma, beta, mean, var, eps, n, cin, cout,
-                        (int64_t)((h + 1) / 2) * (wd / 2), relu, stream, &in, "frh_conv1x1_s2_bn_act");
+  return conv1x1_launch("frh_conv1x1_s2_bn_act", conv1x1_pick_step(cin), x, w, skip, y,
+                        {gamma, beta, mean, var, eps}, n, cin, cout, (int64_t)((h + 1) / 2) * (wd / 2), relu, stream,
+                        /*pre=*/{}, /*pre_relu=*/0, /*in_h=*/h, /*in_w=*/wd);
 }

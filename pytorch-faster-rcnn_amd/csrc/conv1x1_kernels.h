@@ -19,28 +19,24 @@
 //     consecutive floats of one row.
 // Inside a step lane half h owns k = h BK/2 .. h BK/2 + BK/2 - 1 (a fixed permutation of the
 // k order: the sum is over the same products, and the order is the same on every launch).
-// s and b of the tile's 64 channels are computed once per workgroup into LDS with
-// bn_act_kernel's expressions.  Workgroups are numbered cout-tile fastest and dealt to the 8
-// XCDs in contiguous chunks, so the cout tiles that re-read one X tile run on one L2.
+// s and b of the tile's 64 channels are computed once per workgroup into LDS (bn_fold.h holds
+// the BN arithmetic of every form).  Workgroups are numbered cout-tile fastest and dealt to the
+// 8 XCDs in contiguous chunks, so the cout tiles that re-read one X tile run on one L2.
 //
 // Two input-side forms of the same kernel (template flags; the plain instantiations compile
 // to what they were):
 //   PRE: the frozen BN (+ ReLU) that precedes the convolution (a bottleneck's bn2 in front of
 //     conv3) applied to the X registers between the global load and the LDS write, s_in / b_in
-//     of all cin channels computed once per workgroup into LDS with bn_act_kernel's
-//     expressions: the bits of frh_bn_act followed by the plain kernel, without that pass.
+//     of all cin channels computed once per workgroup into LDS: the bits of frh_bn_act
+//     followed by the plain kernel, without that pass.
 //   S2: the X tile gathered from x[:, :, ::2, ::2] of an NCHW input (a stride-2 projection).
 //     With w_out % 4 == 0 a thread's four output pixels lie in one input row and are the
 //     .x / .z of two aligned float4 loads: the bits of the plain kernel on a contiguous copy
 //     of the subsampled input.
 #pragma once
-#include <math.h>
-
-#include "common.h"
+#include "bn_fold.h"
 
 namespace frh {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kCxThreads = 256;
 constexpr int kCxTile = 64;  // outputs per workgroup: kCxTile channels x kCxTile pixels
@@ -52,34 +48,20 @@ struct Conv1x1Args {
   const float* w;
   const float* skip;
   float* y;
-  const float* gamma;
-  const float* beta;
-  const float* mean;
-  const float* var;
-  float eps;
+  FrozenBN bn;
   int cin, cout;
   int64_t hw;
   int mt, pt;     // cout tiles, pixel tiles per image
   int64_t total;  // mt * pt * n
   int64_t chunk;  // ceil(total / kCxXcds)
   int relu;
-  // PRE: the BN in front of the convolution (beta / gamma may be NULL)
-  const float* pre_gamma;
-  const float* pre_beta;
-  const float* pre_mean;
-  const float* pre_var;
-  float pre_eps;
+  // PRE: the BN in front of the convolution
+  FrozenBN pre;
   int pre_relu;
   // S2: the input plane (hw is the output plane, w_out its row length)
   int64_t in_hw;
   int in_w, w_out;
 };
-
-__device__ __forceinline__ float4 conv1x1_pre(float4 v, float s, float b, int relu) {
-  float4 r = make_float4(v.x * s + b, v.y * s + b, v.z * s + b, v.w * s + b);
-  if (relu) r = make_float4(fmaxf(r.x, 0.0f), fmaxf(r.y, 0.0f), fmaxf(r.z, 0.0f), fmaxf(r.w, 0.0f));
-  return r;
-}
 
 template <int BK, bool PRE = false, bool S2 = false>
 __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x1Args a) {
@@ -108,20 +90,11 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
   const int h = lane >> 5, j = lane & 31;
 
   // read in the epilogue, after the main loop's barriers
-  const bool bn = a.mean != nullptr;
-  if (bn && tid < T) {
-    const int c = m0 + tid;
-    const float s = (a.gamma ? a.gamma[c] : 1.0f) / sqrtf(a.var[c] + a.eps);
-    bn_s[tid] = s;
-    bn_b[tid] = (a.beta ? a.beta[c] : 0.0f) - a.mean[c] * s;
-  }
+  const bool bn = a.bn.mean != nullptr;
+  if (bn && tid < T) bn_fold(a.bn, m0 + tid, bn_s[tid], bn_b[tid]);
 
   if constexpr (PRE) {
-    for (int c = tid; c < a.cin; c += kCxThreads) {
-      const float s = (a.pre_gamma ? a.pre_gamma[c] : 1.0f) / sqrtf(a.pre_var[c] + a.pre_eps);
-      pre_s[c] = s;
-      pre_b[c] = (a.pre_beta ? a.pre_beta[c] : 0.0f) - a.pre_mean[c] * s;
-    }
+    for (int c = tid; c < a.cin; c += kCxThreads) bn_fold(a.pre, c, pre_s[c], pre_b[c]);
     __syncthreads();  // step 0 transforms its registers before the loop's first barrier
   }
 
@@ -172,8 +145,8 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
     float4 vb1 = S2 ? make_float4(rb1.x, rb1.z, rc1.x, rc1.z) : rb1;
     if constexpr (PRE) {
       const int c = t * BK + b_row;
-      vb0 = conv1x1_pre(vb0, pre_s[c], pre_b[c], a.pre_relu);
-      if (NV > 1) vb1 = conv1x1_pre(vb1, pre_s[c + B_ROWS], pre_b[c + B_ROWS], a.pre_relu);
+      vb0 = bn_apply(vb0, true, &pre_s[c], &pre_b[c], false, nullptr, a.pre_relu);
+      if (NV > 1) vb1 = bn_apply(vb1, true, &pre_s[c + B_ROWS], &pre_b[c + B_ROWS], false, nullptr, a.pre_relu);
     }
     *reinterpret_cast<float4*>(&Bs[buf][b_row * PB + b_q * 4]) = vb0;
     if (NV > 1) *reinterpret_cast<float4*>(&Bs[buf][(b_row + B_ROWS) * PB + b_q * 4]) = vb1;
@@ -194,8 +167,8 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
   }
 #undef FRH_CX_LOAD
 
-  // epilogue: bn_act_kernel's four operations in its order, on the accumulator.  Register r of
-  // the 32 x 32 tile is row (r & 3) + 8 (r >> 2) + 4 h, column j.
+  // epilogue: bn_fold.h's bn_apply on the accumulator; register r of the 32 x 32 tile is row
+  // mfma32_row(r) + 4 h, column j.
   const int64_t p = p0 + wn * 32 + j;
   if (p >= a.hw) return;
   const int lrow = wm * 32 + 4 * h;
@@ -203,16 +176,13 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
   float k[16];
   if (a.skip) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) k[r] = a.skip[off + (int64_t)((r & 3) + 8 * (r >> 2)) * a.hw];
+    for (int r = 0; r < 16; ++r) k[r] = a.skip[off + (int64_t)mfma32_row(r) * a.hw];
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int lr = lrow + (r & 3) + 8 * (r >> 2);
-    float v = acc[r];
-    if (bn) v = v * bn_s[lr] + bn_b[lr];
-    if (a.skip) v = v + k[r];
-    if (a.relu) v = fmaxf(v, 0.0f);
-    a.y[off + (int64_t)((r & 3) + 8 * (r >> 2)) * a.hw] = v;
+    const int lr = lrow + mfma32_row(r);
+    a.y[off + (int64_t)mfma32_row(r) * a.hw] =
+        bn_apply(acc[r], bn, &bn_s[lr], &bn_b[lr], a.skip != nullptr, &k[r], a.relu);
   }
 }
 
@@ -220,50 +190,30 @@ __global__ void __launch_bounds__(kCxThreads) conv1x1_bn_act_kernel(const Conv1x
 // tools/bench_conv1x1.py.
 inline int conv1x1_pick_step(int32_t cin) { return cin >= 128 && cin % 32 == 0 ? 32 : 16; }
 
-// The input-side forms: pre != NULL is PRE (its mean / var given), in_w > 0 is S2 (x is
-// [n, cin, in_h, in_w], hw the output plane ((in_h + 1) / 2) * (in_w / 2)); not both.
-struct Conv1x1Input {
-  const float* pre_gamma = nullptr;
-  const float* pre_beta = nullptr;
-  const float* pre_mean = nullptr;
-  const float* pre_var = nullptr;
-  float pre_eps = 0.0f;
-  int32_t pre_relu = 0;
-  int32_t in_h = 0, in_w = 0;
-};
-
-inline int32_t conv1x1_launch(int step, const float* x, const float* w, const float* skip, float* y,
-                              const float* gamma, const float* beta, const float* mean, const float* var, float eps,
-                              int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream,
-                              const Conv1x1Input* in = nullptr, const char* what = "frh_conv1x1_bn_act") {
-  const bool pre = in && in->pre_mean, s2 = in && in->in_w > 0;
+// The input-side forms: pre.mean != NULL is PRE, in_w > 0 is S2 (x is [n, cin, in_h, in_w] with
+// in_w % 8 == 0, hw the output plane ((in_h + 1) / 2) * (in_w / 2)); not both.
+inline int32_t conv1x1_launch(const char* what, int step, const float* x, const float* w, const float* skip, float* y,
+                              FrozenBN bn, int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu,
+                              void* stream, FrozenBN pre = {}, int32_t pre_relu = 0, int32_t in_h = 0,
+                              int32_t in_w = 0) {
+  const bool s2 = in_w > 0;
   FRH_REQUIRE(n >= 0 && cin >= 1 && cout >= 1 && hw >= 0, "bad sizes");
   if (n == 0 || hw == 0) return FRH_OK;
   FRH_REQUIRE(x && w && y, "null pointer argument");
-  FRH_REQUIRE((mean == nullptr) == (var == nullptr), "mean and var must both be given or both be NULL");
+  FRH_REQUIRE_BN_PAIR(bn);
   FRH_REQUIRE(hw % 4 == 0, "plane size %lld must be a multiple of 4", (long long)hw);
   FRH_REQUIRE(cin % 16 == 0 && cout % kCxTile == 0, "cin %d must be a multiple of 16 and cout %d of 64", cin, cout);
-  FRH_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)skip | (uintptr_t)w) % 16 == 0,
-              "tensors must be 16-byte aligned");
-  FRH_REQUIRE(y != x && y != skip, "y must not alias x or skip");
+  FRH_REQUIRE_ALIGNED16(x, y, skip, w);
+  const int64_t in_hw = s2 ? (int64_t)in_h * in_w : hw, yb = n * cout * hw * 4;
+  FRH_REQUIRE(!ranges_overlap(y, yb, x, n * cin * in_hw * 4) && !ranges_overlap(y, yb, w, (int64_t)cout * cin * 4) &&
+                  !(skip && ranges_overlap(y, yb, skip, yb)),
+              "y must not alias x, w or skip");
   FRH_REQUIRE((step == 16 || step == 32) && cin % step == 0, "step %d does not fit cin %d", step, cin);
-  FRH_REQUIRE(!(pre && s2), "the input BN and the stride-2 gather are separate forms");
+  FRH_REQUIRE(!(pre.mean && s2), "the input BN and the stride-2 gather are separate forms");
+  FRH_REQUIRE(!pre.mean || cin <= kCxPreMax, "cin %d above the input BN form's bound %d", cin, kCxPreMax);
   Conv1x1Args a;
-  a.pre_gamma = a.pre_beta = a.pre_mean = a.pre_var = nullptr, a.pre_eps = 0.0f, a.pre_relu = 0;
-  a.in_hw = 0, a.in_w = a.w_out = 0;
-  if (in && !s2) {
-    FRH_REQUIRE(in->pre_mean && in->pre_var, "the input BN needs its mean and var");
-    FRH_REQUIRE(cin <= kCxPreMax, "cin %d above the input BN form's bound %d", cin, kCxPreMax);
-    a.pre_gamma = in->pre_gamma, a.pre_beta = in->pre_beta, a.pre_mean = in->pre_mean, a.pre_var = in->pre_var;
-    a.pre_eps = in->pre_eps, a.pre_relu = in->pre_relu;
-  }
-  if (s2) {
-    FRH_REQUIRE(in->in_h >= 1 && in->in_w % 8 == 0,
-                "input width %d must be a multiple of 8 (output width a multiple of 4)", in->in_w);
-    FRH_REQUIRE(hw == (int64_t)((in->in_h + 1) / 2) * (in->in_w / 2), "output plane does not match the input");
-    a.in_hw = (int64_t)in->in_h * in->in_w, a.in_w = in->in_w, a.w_out = in->in_w / 2;
-  }
-  a.x = x, a.w = w, a.skip = skip, a.y = y, a.gamma = gamma, a.beta = beta, a.mean = mean, a.var = var, a.eps = eps;
+  a.x = x, a.w = w, a.skip = skip, a.y = y, a.bn = bn, a.pre = pre, a.pre_relu = pre_relu;
+  a.in_hw = in_hw, a.in_w = in_w, a.w_out = in_w / 2;
   a.cin = cin, a.cout = cout, a.hw = hw, a.relu = relu;
   a.mt = cout / kCxTile;
   const int64_t pt = (hw + kCxTile - 1) / kCxTile;
@@ -273,20 +223,15 @@ inline int32_t conv1x1_launch(int step, const float* x, const float* w, const fl
   a.chunk = (a.total + kCxXcds - 1) / kCxXcds;
   FRH_REQUIRE(a.chunk * kCxXcds < ((int64_t)1 << 31), "too many blocks");
   const dim3 grid((unsigned)(a.chunk * kCxXcds)), block(kCxThreads);
-#define FRH_CX_GO(PRE, S2)                                                                             \
-  do {                                                                                                 \
-    if (step == 32)                                                                                    \
-      hipLaunchKernelGGL((conv1x1_bn_act_kernel<32, PRE, S2>), grid, block, 0, as_stream(stream), a);  \
-    else                                                                                               \
-      hipLaunchKernelGGL((conv1x1_bn_act_kernel<16, PRE, S2>), grid, block, 0, as_stream(stream), a);  \
-  } while (0)
-  if (pre)
-    FRH_CX_GO(true, false);
+  auto go = [&](auto k16, auto k32) {
+    hipLaunchKernelGGL(step == 32 ? k32 : k16, grid, block, 0, as_stream(stream), a);
+  };
+  if (pre.mean)
+    go(conv1x1_bn_act_kernel<16, true, false>, conv1x1_bn_act_kernel<32, true, false>);
   else if (s2)
-    FRH_CX_GO(false, true);
+    go(conv1x1_bn_act_kernel<16, false, true>, conv1x1_bn_act_kernel<32, false, true>);
   else
-    FRH_CX_GO(false, false);
-#undef FRH_CX_GO
+    go(conv1x1_bn_act_kernel<16, false, false>, conv1x1_bn_act_kernel<32, false, false>);
   return check_launch(what);
 }
 

@@ -41,7 +41,6 @@
 
 namespace frh {
 
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWgThreads = 256;
@@ -329,7 +328,7 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
     FRH_WG_SYNC();                                                                  \
   } while (0)
 
-  wg_f32x16 acc[16];
+  f32x16 acc[16];
 #pragma unroll
   for (int p = 0; p < 16; ++p)
 #pragma unroll
@@ -360,7 +359,7 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
 #undef FRH_WG_STEP
 
   // epilogue: Y = A^T M A, + bias, ReLU.  Register r of a 32 x 32 tile is row (tile)
-  // (r & 3) + 8 (r >> 2) + 4 h: tile row r >> 2 of the wave's four, tile column (r & 3) + 4 h.
+  // mfma32_row(r) + 4 h: tile row r >> 2 of the wave's four, tile column (r & 3) + 4 h.
   const int co = cb * kWgCout + wn * 32 + j;
   const bool has_bias = L.bias != nullptr;
   const float bias = has_bias ? L.bias[co] : 0.0f;
@@ -412,7 +411,7 @@ inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3Lev
   FRH_REQUIRE(cin % kWgBK == 0 && cout % kWgCout == 0, "cin %d must be a multiple of %d and cout %d of %d", cin,
               kWgBK, cout, kWgCout);
   FRH_REQUIRE(ws, "null pointer argument");
-  FRH_REQUIRE((uintptr_t)ws % 16 == 0, "tensors must be 16-byte aligned");
+  FRH_REQUIRE_ALIGNED16(ws);
   const int64_t slot = (int64_t)16 * cin * cout;
   Conv3x3Weights tab = {};
   int slots = 0;
@@ -424,8 +423,7 @@ inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3Lev
     FRH_REQUIRE(s.h >= 0 && s.w >= 0, "bad sizes");
     if (n == 0 || s.h == 0 || s.w == 0) continue;
     FRH_REQUIRE(s.x && s.y && s.wt, "null pointer argument");
-    FRH_REQUIRE(((uintptr_t)s.x | (uintptr_t)s.y | (uintptr_t)s.bias | (uintptr_t)s.wt) % 16 == 0,
-                "tensors must be 16-byte aligned");
+    FRH_REQUIRE_ALIGNED16(s.x, s.y, s.bias, s.wt);
     if (slots == 0 || tab.w[slots - 1] != s.wt) {
       FRH_REQUIRE((slots + 1) * slot <= ws_floats, "workspace holds %lld floats, %d weights need %lld",
                   (long long)ws_floats, slots + 1, (long long)((slots + 1) * slot));
@@ -437,8 +435,8 @@ inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3Lev
     const int64_t span = (int64_t)(s.h - 1) * s.sy + (int64_t)(s.w - 1) * s.sx + cin;
     FRH_REQUIRE(span < ((int64_t)1 << 30), "one image of x spans too many elements");
     const int64_t x_end = (n - 1) * s.sn + span, y_end = n * s.h * s.w * cout;
-    FRH_REQUIRE(s.y + y_end <= s.x || s.x + x_end <= s.y, "y must not alias x");
-    FRH_REQUIRE(s.y + y_end <= ws || ws + ws_floats <= s.y, "y must not alias the workspace");
+    FRH_REQUIRE(!ranges_overlap(s.y, y_end * 4, s.x, x_end * 4), "y must not alias x");
+    FRH_REQUIRE(!ranges_overlap(s.y, y_end * 4, ws, ws_floats * 4), "y must not alias the workspace");
     Conv3x3Level& L = a.lv[a.levels++];
     L.x = s.x, L.u = tab.u[slots - 1], L.bias = s.bias, L.y = s.y;
     L.sn = s.sn, L.sy = (int32_t)s.sy, L.sx = (int32_t)s.sx, L.h = s.h, L.w = s.w;

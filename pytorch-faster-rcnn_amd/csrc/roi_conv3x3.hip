@@ -15,5 +15,5 @@ extern "C" int32_t frh_roi_conv3x3_bn_act(const float* x, const float* w, float*
                                           const float* beta, const float* mean, const float* var, float eps,
                                           int64_t r, int32_t cin, int32_t cout, int32_t relu, float* workspace,
                                           void* stream) {
-  return roi_conv3x3_launch(x, w, y, gamma, beta, mean, var, eps, r, cin, cout, relu, workspace, stream);
+  return roi_conv3x3_launch(x, w, y, {gamma, beta, mean, var, eps}, r, cin, cout, relu, workspace, stream);
 }

@@ -26,14 +26,9 @@
 // fixed permutation of the (ci, tap) order, the same for every column, launch and r.  Columns of
 // an MFMA never mix, so a RoI's bits do not depend on its neighbours, its index or r.
 #pragma once
-#include <math.h>
-
-#include "common.h"
+#include "bn_fold.h"
 
 namespace frh {
-
-typedef float rc_f32x16 __attribute__((ext_vector_type(16)));
-typedef float rc_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRcRois = 4;                             // RoIs per workgroup
 constexpr int kRcKc = 8;                               // input channels per chunk
@@ -47,11 +42,7 @@ struct RoiConvArgs {
   const float* x;
   const float* wp;  // repacked weights (workspace)
   float* y;
-  const float* gamma;
-  const float* beta;
-  const float* mean;
-  const float* var;
-  float eps;
+  FrozenBN bn;
   int64_t r;
   int cin, cout;
   int mt;  // channel blocks of WM * 32
@@ -97,19 +88,14 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
   const int m0 = mb * MB;
 
   // read in the epilogue, after the main loop's barriers
-  const bool bn = a.mean != nullptr;
-  if (bn && tid < MB) {
-    const int c = m0 + tid;
-    const float s = (a.gamma ? a.gamma[c] : 1.0f) / sqrtf(a.var[c] + a.eps);
-    bn_s[tid] = s;
-    bn_b[tid] = (a.beta ? a.beta[c] : 0.0f) - a.mean[c] * s;
-  }
+  const bool bn = a.bn.mean != nullptr;
+  if (bn && tid < MB) bn_fold(a.bn, m0 + tid, bn_s[tid], bn_b[tid]);
   for (int i = tid; i < kRcXs; i += NT) Bs[i] = 0.0f;
   __syncthreads();  // the zero borders stand before any interior is written
 
   // X staging: float4 v of the chunk (v < 392) is RoI v / 98, elements 4 (v % 98) .. + 3 of that
   // RoI's 8 x 49 contiguous floats; element e is channel e / 49, position e % 49.
-  const rc_f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
   const float* xsrc[XV];
   int xdst[XV][4];
   bool xok[XV];
@@ -126,14 +112,14 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
     }
   }
   const int chunks = a.cin / kRcKc;
-  const rc_f32x4* wsrc = reinterpret_cast<const rc_f32x4*>(a.wp + (int64_t)mb * chunks * AS) + tid;
-  rc_f32x4 ra[AV], rx[XV];
+  const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wp + (int64_t)mb * chunks * AS) + tid;
+  f32x4 ra[AV], rx[XV];
   auto load = [&](int t) {
 #pragma unroll
     for (int u = 0; u < AV; ++u) ra[u] = wsrc[(int64_t)t * (AS / 4) + u * NT];
 #pragma unroll
     for (int u = 0; u < XV; ++u)
-      rx[u] = xok[u] ? *reinterpret_cast<const rc_f32x4*>(xsrc[u] + (int64_t)t * (kRcKc * kRcTile)) : z4;
+      rx[u] = xok[u] ? *reinterpret_cast<const f32x4*>(xsrc[u] + (int64_t)t * (kRcKc * kRcTile)) : z4;
   };
 
   // this lane's seven columns: block cb, column j -> (RoI, y, x); idle columns read column 0
@@ -147,7 +133,7 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
   }
   const int abase = h * MB + wave * 32 + j;
 
-  rc_f32x16 acc[kRcBlocks];
+  f32x16 acc[kRcBlocks];
 #pragma unroll
   for (int cb = 0; cb < kRcBlocks; ++cb)
 #pragma unroll
@@ -156,7 +142,7 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
   load(0);
   for (int t = 0; t < chunks; ++t) {
 #pragma unroll
-    for (int u = 0; u < AV; ++u) *reinterpret_cast<rc_f32x4*>(&As[(tid + u * NT) * 4]) = ra[u];
+    for (int u = 0; u < AV; ++u) *reinterpret_cast<f32x4*>(&As[(tid + u * NT) * 4]) = ra[u];
 #pragma unroll
     for (int u = 0; u < XV; ++u) {
       if (xdst[u][0] >= 0) {
@@ -189,8 +175,8 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
     __syncthreads();  // every wave has read this chunk before the next one is written
   }
 
-  // epilogue: bn_act_kernel's operations in its order, on the accumulator.  Register r of a
-  // 32 x 32 tile is row (r & 3) + 8 (r >> 2) + 4 h, column j.
+  // epilogue: bn_fold.h's bn_apply on the accumulators; register r of a 32 x 32 tile is row
+  // mfma32_row(r) + 4 h, column j.
   const int lrow = wave * 32 + 4 * h;
 #pragma unroll
   for (int cb = 0; cb < kRcBlocks; ++cb) {
@@ -200,39 +186,29 @@ __global__ void __launch_bounds__(WM * 64, WM == 4 ? 2 : 1) roi_conv3x3_bn_act_k
     float* yp = a.y + ((roi0 + rl) * a.cout + m0 + lrow) * kRcTile + p;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int dr = (r & 3) + 8 * (r >> 2);
-      float v = acc[cb][r];
-      if (bn) v = v * bn_s[lrow + dr] + bn_b[lrow + dr];
-      if (a.relu) v = fmaxf(v, 0.0f);
-      yp[dr * kRcTile] = v;
+      const int dr = mfma32_row(r);
+      yp[dr * kRcTile] = bn_apply(acc[cb][r], bn, &bn_s[lrow + dr], &bn_b[lrow + dr], false, nullptr, a.relu);
     }
   }
 }
 
-inline bool rc_overlap(const void* p, int64_t pn, const void* q, int64_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)qn && b < a + (uintptr_t)pn;
-}
-
-inline int32_t roi_conv3x3_launch(const float* x, const float* w, float* y, const float* gamma, const float* beta,
-                                  const float* mean, const float* var, float eps, int64_t r, int32_t cin,
+inline int32_t roi_conv3x3_launch(const float* x, const float* w, float* y, FrozenBN bn, int64_t r, int32_t cin,
                                   int32_t cout, int32_t relu, float* workspace, void* stream) {
   FRH_REQUIRE(r >= 0 && cin >= 1 && cout >= 1, "bad sizes");
   FRH_REQUIRE(cin % 16 == 0 && cout % 64 == 0, "cin %d must be a multiple of 16 and cout %d of 64", cin, cout);
   if (r == 0) return FRH_OK;
   FRH_REQUIRE(x && w && y && workspace, "null pointer argument");
-  FRH_REQUIRE((mean == nullptr) == (var == nullptr), "mean and var must both be given or both be NULL");
-  FRH_REQUIRE(((uintptr_t)x | (uintptr_t)y | (uintptr_t)w | (uintptr_t)workspace) % 16 == 0,
-              "tensors must be 16-byte aligned");
+  FRH_REQUIRE_BN_PAIR(bn);
+  FRH_REQUIRE_ALIGNED16(x, y, w, workspace);
   FRH_REQUIRE(r < ((int64_t)1 << 40), "too many RoIs");
   const int64_t xb = r * cin * kRcTile * 4, yb = r * cout * kRcTile * 4, wb = (int64_t)cin * cout * 9 * 4;
-  FRH_REQUIRE(!rc_overlap(y, yb, x, xb) && !rc_overlap(y, yb, workspace, wb) && !rc_overlap(y, yb, w, wb),
+  FRH_REQUIRE(!ranges_overlap(y, yb, x, xb) && !ranges_overlap(y, yb, workspace, wb) && !ranges_overlap(y, yb, w, wb),
               "y must not overlap x, w or the workspace");
-  FRH_REQUIRE(!rc_overlap(workspace, wb, x, xb) && !rc_overlap(workspace, wb, w, wb),
+  FRH_REQUIRE(!ranges_overlap(workspace, wb, x, xb) && !ranges_overlap(workspace, wb, w, wb),
               "the workspace must not overlap x or w");
   const int wm = cout % 128 == 0 ? 4 : 2;
   RoiConvArgs a;
-  a.x = x, a.wp = workspace, a.y = y, a.gamma = gamma, a.beta = beta, a.mean = mean, a.var = var, a.eps = eps;
+  a.x = x, a.wp = workspace, a.y = y, a.bn = bn;
   a.r = r, a.cin = cin, a.cout = cout, a.relu = relu;
   a.mt = cout / (wm * 32);
   const int64_t blocks = (r + kRcRois - 1) / kRcRois * a.mt;

@@ -755,8 +755,6 @@ struct QuadLayout {
 constexpr int quad_max_cells(int ph, int pw) { return (4 * ph) * ((4 * pw) | 1); }
 static_assert(quad_max_cells(7, 7) <= QuadLayout<1>::kCells, "7x7 tap grids must fit one slab");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <int OFF>
 __device__ __forceinline__ f32x4 lds_read_b128(uint32_t addr) {
   f32x4 v;

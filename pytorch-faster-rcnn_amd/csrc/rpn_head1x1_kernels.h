@@ -25,8 +25,6 @@
 
 namespace frh {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRhThreads = 256;
 constexpr int kRhPix = 64;       // pixels per tile
 constexpr int kRhCols = 16;      // output channels (MFMA columns), c_cls + c_reg padded
@@ -189,7 +187,7 @@ inline int32_t rpn_head1x1_launch(int32_t levels, const RpnHeadLevelDesc* d, con
   FRH_REQUIRE(c_cls + c_reg <= kRhCols, "%d + %d output channels, at most %d together", c_cls, c_reg, kRhCols);
   FRH_REQUIRE(cin % 8 == 0 && cin <= kRhMaxCin, "cin %d must be a multiple of 8 and at most %d", cin, kRhMaxCin);
   FRH_REQUIRE((c_cls == 0 || w_cls) && (c_reg == 0 || w_reg), "null pointer argument");
-  FRH_REQUIRE(((uintptr_t)w_cls | (uintptr_t)w_reg) % 16 == 0, "tensors must be 16-byte aligned");
+  FRH_REQUIRE_ALIGNED16(w_cls, w_reg);
   RpnHeadArgs a;
   a.levels = 0, a.cin = cin, a.c_cls = c_cls, a.c_reg = c_reg;
   a.w_cls = w_cls, a.b_cls = b_cls, a.w_reg = w_reg, a.b_reg = b_reg;
@@ -199,7 +197,7 @@ inline int32_t rpn_head1x1_launch(int32_t levels, const RpnHeadLevelDesc* d, con
     FRH_REQUIRE(s.h >= 0 && s.w >= 0, "bad sizes");
     if (n == 0 || s.h == 0 || s.w == 0) continue;
     FRH_REQUIRE(s.x && (c_cls == 0 || s.cls) && (c_reg == 0 || s.reg), "null pointer argument");
-    FRH_REQUIRE((uintptr_t)s.x % 16 == 0, "tensors must be 16-byte aligned");
+    FRH_REQUIRE_ALIGNED16(s.x);
     // the stride of an extent of 1 is never used (torch leaves it arbitrary)
     const int64_t sn = n > 1 ? s.sn : 0, sy = s.h > 1 ? s.sy : 0, sx = s.w > 1 ? s.sx : 0;
     FRH_REQUIRE(sn >= 0 && sy >= 0 && sx >= 0 && (sn | sy | sx) % 4 == 0,

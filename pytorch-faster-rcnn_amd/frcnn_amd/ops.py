@@ -1199,20 +1199,54 @@ class _FrozenBNAct(torch.autograd.Function):
         return gx, gskip, gw, gb, None, None, None, None
 
 
+# The clauses the *_fused_ok predicates below are made of.
+def _f32_hip_4d(x):
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+
+
+def _conv_is(conv, k, stride, padding):
+    """A k x k Conv2d of this stride and zero padding, undilated, ungrouped, with an f32 weight."""
+    return (conv.kernel_size == (k, k) and conv.stride == (stride, stride) and conv.padding == (padding, padding)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
+            and conv.weight.dtype == torch.float32)
+
+
+def _frozen_bn(bn):
+    """An eval-mode BN that normalises with running statistics (without them, PyTorch takes the
+    batch's even in eval mode: the module path)."""
+    return not bn.training and bn.running_mean is not None and bn.running_var is not None
+
+
+def _aligned16(*tensors):
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _bn_args(bn):
+    """gamma, beta, mean, var, eps as the frh_* entries take them."""
+    return ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps)
+
+
+def _level_geometry(xs):
+    """The per-level arrays of the *_levels entries: (h, w) of every level, and its image / row /
+    column strides."""
+    return (i32_array([v for x in xs for v in x.shape[2:]]),
+            i64_array([v for x in xs for v in (x.stride(0), x.stride(2), x.stride(3))]))
+
+
 def bn_act(x, bn, skip=None, relu=True):
     """act(bn(x) (+ skip)) for an eval-mode BatchNorm2d in one HIP pass (frh_bn_act).
-    A BN in training mode (the reference never trains BN statistics) or CPU tensors take
-    the plain module ops."""
-    if bn.training or not x.is_cuda or x.dtype != torch.float32 or (x.shape[2] * x.shape[3]) % 4:
+    A BN in training mode (the reference never trains BN statistics), one without running
+    statistics, or CPU tensors take the plain module ops."""
+    if not (_frozen_bn(bn) and _f32_hip_4d(x)) or (x.shape[2] * x.shape[3]) % 4:
         y = bn(x)
         if skip is not None:
             y = y + skip
         return torch.relu_(y) if relu else y
     return _FrozenBNAct.apply(x, skip, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
-
-
-def _needs_grad(*tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 # Channel classes (cin, cout) at which tools/bench_conv1x1.py measured frh_conv1x1_bn_act slower
@@ -1221,22 +1255,24 @@ def _needs_grad(*tensors):
 _CONV1X1_EXCLUDED = frozenset([(512, 128), (512, 256), (1024, 256), (1024, 512), (2048, 512)])
 
 
+def _conv_bn_fused_ok(conv, bn, x, k, stride, padding):
+    """What the fused conv + frozen-BN entries share: a contiguous NCHW f32 HIP input, a bias-free
+    conv of this geometry with a contiguous weight, cin % 16 == 0, cout % 64 == 0, 16-byte
+    alignment, and no gradient needed."""
+    return (_f32_hip_4d(x) and x.is_contiguous() and _frozen_bn(bn) and conv.bias is None
+            and _conv_is(conv, k, stride, padding) and conv.weight.is_contiguous()
+            and x.shape[1] == conv.in_channels and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0
+            and _aligned16(x, conv.weight) and not _needs_grad(x, conv.weight, bn.weight, bn.bias))
+
+
 def conv1x1_fused_ok(conv, bn, x, skip=None):
     """Whether conv1x1_bn_act takes the fused HIP entry for these arguments."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
-            and not bn.training and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.weight.is_contiguous()):
+    if not _conv_bn_fused_ok(conv, bn, x, 1, 1, 0) or (x.shape[2] * x.shape[3]) % 4 \
+            or (conv.in_channels, conv.out_channels) in _CONV1X1_EXCLUDED:
         return False
-    cout, cin, hw = conv.out_channels, conv.in_channels, x.shape[2] * x.shape[3]
-    if x.shape[1] != cin or hw % 4 or cin % 16 or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16 \
-            or (cin, cout) in _CONV1X1_EXCLUDED:
-        return False
-    if skip is not None and not (skip.is_cuda and skip.dtype == torch.float32 and skip.is_contiguous()
-                                 and skip.shape == (x.shape[0], cout, x.shape[2], x.shape[3])
-                                 and skip.data_ptr() % 16 == 0):
-        return False
-    return not _needs_grad(x, skip, conv.weight, bn.weight, bn.bias)
+    return skip is None or (skip.is_cuda and skip.dtype == torch.float32 and skip.is_contiguous()
+                            and skip.shape == (x.shape[0], conv.out_channels, x.shape[2], x.shape[3])
+                            and _aligned16(skip) and not _needs_grad(skip))
 
 
 # Channel classes (cin, cout) at which tools/bench_conv1x1.py measured frh_conv1x1_bn_act_pre /
@@ -1248,7 +1284,7 @@ _CONV1X1_PRE_MAX_CIN = 512
 
 def conv1x1_pre_fused_ok(conv, bn, x, pre_bn, skip=None):
     """Whether conv1x1_bn_act folds pre_bn (+ ReLU) into the fused entry's input side."""
-    return (conv1x1_fused_ok(conv, bn, x, skip) and not pre_bn.training and pre_bn.running_mean is not None
+    return (conv1x1_fused_ok(conv, bn, x, skip) and _frozen_bn(pre_bn)
             and pre_bn.num_features == conv.in_channels and conv.in_channels <= _CONV1X1_PRE_MAX_CIN
             and (conv.in_channels, conv.out_channels) not in _CONV1X1_PRE_EXCLUDED
             and not _needs_grad(pre_bn.weight, pre_bn.bias))
@@ -1269,30 +1305,18 @@ def conv1x1_bn_act(conv, bn, x, skip=None, relu=True, pre_bn=None):
     n, _, h, w = x.shape
     y = torch.empty(n, conv.out_channels, h, w, dtype=torch.float32, device=x.device)
     if pre_bn is not None:
-        call('frh_conv1x1_bn_act_pre', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), ptr(bn.weight), ptr(bn.bias),
-             ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(pre_bn.weight), ptr(pre_bn.bias),
-             ptr(pre_bn.running_mean), ptr(pre_bn.running_var), float(pre_bn.eps), 1, n, conv.in_channels,
-             conv.out_channels, h * w, int(bool(relu)), stream_of(x))
+        call('frh_conv1x1_bn_act_pre', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), *_bn_args(bn), *_bn_args(pre_bn), 1,
+             n, conv.in_channels, conv.out_channels, h * w, int(bool(relu)), stream_of(x))
         return y
-    call('frh_conv1x1_bn_act', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), ptr(bn.weight), ptr(bn.bias),
-         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), n, conv.in_channels, conv.out_channels, h * w,
-         int(bool(relu)), stream_of(x))
+    call('frh_conv1x1_bn_act', ptr(x), ptr(conv.weight), ptr(skip), ptr(y), *_bn_args(bn), n, conv.in_channels,
+         conv.out_channels, h * w, int(bool(relu)), stream_of(x))
     return y
 
 
 def conv1x1_s2_fused_ok(conv, bn, x):
     """Whether conv1x1_s2_bn_act takes the fused HIP entry for these arguments."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
-            and not bn.training and bn.running_mean is not None and conv.bias is None
-            and conv.weight.dtype == torch.float32 and conv.kernel_size == (1, 1) and conv.stride == (2, 2)
-            and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.weight.is_contiguous()):
-        return False
-    cout, cin = conv.out_channels, conv.in_channels
-    if x.shape[1] != cin or x.shape[0] == 0 or x.shape[2] == 0 or x.shape[3] == 0 or x.shape[3] % 8 or cin % 16 \
-            or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16 or (cin, cout) in _CONV1X1_S2_EXCLUDED:
-        return False
-    return not _needs_grad(x, conv.weight, bn.weight, bn.bias)
+    return (_conv_bn_fused_ok(conv, bn, x, 1, 2, 0) and x.numel() > 0 and x.shape[3] % 8 == 0
+            and (conv.in_channels, conv.out_channels) not in _CONV1X1_S2_EXCLUDED)
 
 
 def conv1x1_s2_bn_act(conv, bn, x, relu=False):
@@ -1304,9 +1328,8 @@ def conv1x1_s2_bn_act(conv, bn, x, relu=False):
         return bn_act(conv(x), bn, relu=relu)
     n, _, h, w = x.shape
     y = torch.empty(n, conv.out_channels, (h + 1) // 2, w // 2, dtype=torch.float32, device=x.device)
-    call('frh_conv1x1_s2_bn_act', ptr(x), ptr(conv.weight), None, ptr(y), ptr(bn.weight), ptr(bn.bias),
-         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), n, conv.in_channels, conv.out_channels, h, w,
-         int(bool(relu)), stream_of(x))
+    call('frh_conv1x1_s2_bn_act', ptr(x), ptr(conv.weight), None, ptr(y), *_bn_args(bn), n, conv.in_channels,
+         conv.out_channels, h, w, int(bool(relu)), stream_of(x))
     return y
 
 
@@ -1315,10 +1338,8 @@ _RPN_HEAD1X1_MAX_CIN = 256
 
 
 def _plain_1x1(conv):
-    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.weight.dtype == torch.float32
-            and conv.weight.stride(0) == conv.in_channels and conv.weight.stride(1) == 1
-            and conv.weight.data_ptr() % 16 == 0
+    return (_conv_is(conv, 1, 1, 0) and conv.weight.stride(0) == conv.in_channels and conv.weight.stride(1) == 1
+            and _aligned16(conv.weight)
             and (conv.bias is None or (conv.bias.dtype == torch.float32 and conv.bias.is_contiguous())))
 
 
@@ -1333,10 +1354,10 @@ def rpn_head1x1_fused_ok(classifier, regressor, hidden):
         return False
     x0 = hidden[0]
     for x in hidden:
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.device == x0.device
+        if not (_f32_hip_4d(x) and x.device == x0.device
                 and x.shape[0] == x0.shape[0] and x.shape[1] == cin and x.numel() > 0 and x.stride(1) == 1
                 and (x.shape[2] * x.shape[3] == 1 or _suggests_channels_last(x))
-                and x.data_ptr() % 16 == 0 and all(s >= 0 and s % 4 == 0 for i, (d, s) in enumerate(zip(x.shape, x.stride())) if i != 1 and d > 1)
+                and _aligned16(x) and all(s >= 0 and s % 4 == 0 for i, (d, s) in enumerate(zip(x.shape, x.stride())) if i != 1 and d > 1)
                 and x.shape[0] * x.shape[2] * x.shape[3] < 1 << 31):
             return False
     return not _needs_grad(classifier.weight, classifier.bias, regressor.weight, regressor.bias, *hidden)
@@ -1377,8 +1398,7 @@ def rpn_head1x1_levels(classifier, regressor, hidden):
     reg = [out(regressor, x) for x in hidden]
     call('frh_rpn_head1x1_levels', len(hidden), ptr_array(hidden), ptr_array(cls), ptr_array(reg),
          ptr(classifier.weight), ptr(classifier.bias), ptr(regressor.weight), ptr(regressor.bias), n, cin, cc, cr,
-         i32_array([v for x in hidden for v in x.shape[2:]]),
-         i64_array([v for x in hidden for v in (x.stride(0), x.stride(2), x.stride(3))]), stream_of(hidden[0]))
+         *_level_geometry(hidden), stream_of(hidden[0]))
     return cls, reg
 
 
@@ -1386,16 +1406,7 @@ def roi_conv3x3_fused_ok(conv, bn, x):
     """Whether roi_conv3x3_bn_act takes the fused HIP entry for these arguments.  No RoI count is
     excluded: tools/bench_roi_conv.py measured the entry faster than the modules at r = 512, 1000
     and 2000 (both times in DESIGN section 4)."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2:] == (7, 7) and x.is_contiguous()
-            and not bn.training and bn.running_mean is not None and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
-            and conv.weight.is_contiguous()):
-        return False
-    cout, cin = conv.out_channels, conv.in_channels
-    if x.shape[1] != cin or cin % 16 or cout % 64 or (x.data_ptr() | conv.weight.data_ptr()) % 16:
-        return False
-    return not _needs_grad(x, conv.weight, bn.weight, bn.bias)
+    return _conv_bn_fused_ok(conv, bn, x, 3, 1, 1) and x.shape[2:] == (7, 7)
 
 
 def roi_conv3x3_bn_act(conv, bn, x, relu=True):
@@ -1410,9 +1421,8 @@ def roi_conv3x3_bn_act(conv, bn, x, relu=True):
     r = x.shape[0]
     y = torch.empty(r, conv.out_channels, 7, 7, dtype=torch.float32, device=x.device)
     ws = torch.empty(9 * conv.in_channels * conv.out_channels, dtype=torch.float32, device=x.device)
-    call('frh_roi_conv3x3_bn_act', ptr(x), ptr(conv.weight), ptr(y), ptr(bn.weight), ptr(bn.bias),
-         ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), r, conv.in_channels, conv.out_channels,
-         int(bool(relu)), ptr(ws), stream_of(x))
+    call('frh_roi_conv3x3_bn_act', ptr(x), ptr(conv.weight), ptr(y), *_bn_args(bn), r, conv.in_channels,
+         conv.out_channels, int(bool(relu)), ptr(ws), stream_of(x))
     return y
 
 
@@ -1426,9 +1436,7 @@ _CONV3X3_EXCLUDED = frozenset([(38, 64), (19, 32), (10, 16)])
 def conv3x3_fused_ok(conv, x, alone=True):
     """Whether conv3x3_bias_act takes the fused HIP entry for these arguments (alone=False:
     as one level of a multi-level launch, where the size exclusions do not apply)."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.weight.dtype == torch.float32
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
+    if not (_f32_hip_4d(x) and _conv_is(conv, 3, 1, 1)
             and conv.weight.is_contiguous(memory_format=torch.channels_last)):
         return False
     cout, cin = conv.out_channels, conv.in_channels
@@ -1439,9 +1447,7 @@ def conv3x3_fused_ok(conv, x, alone=True):
     if sc != 1 or sx < cin or sy < 0 or sn < 0 or (sn | sy | sx) % 4 \
             or (h - 1) * sy + (w - 1) * sx + cin >= 1 << 30:
         return False
-    if (x.data_ptr() | conv.weight.data_ptr() | (conv.bias.data_ptr() if conv.bias is not None else 0)) % 16:
-        return False
-    return not _needs_grad(x, conv.weight, conv.bias)
+    return _aligned16(x, conv.weight, conv.bias) and not _needs_grad(x, conv.weight, conv.bias)
 
 
 def _conv3x3_ws(cin, cout, dev):
@@ -1489,8 +1495,7 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
     ws = _conv3x3_ws(cin, cout * distinct, dev)
     call('frh_conv3x3_bias_act_levels', len(fx), ptr_array(fx), ptr_array([c.weight for c in fc]),
          _ptrs_or_null([c.bias for c in fc]), ptr_array(ys), ptr(ws), ws.numel() * 4, n, cin, cout,
-         i32_array([v for x in fx for v in x.shape[2:]]),
-         i64_array([v for x in fx for v in (x.stride(0), x.stride(2), x.stride(3))]), int(bool(relu)), stream_of(fx[0]))
+         *_level_geometry(fx), int(bool(relu)), stream_of(fx[0]))
     for i, y in zip(fused, ys):
         outs[i] = y
     return outs
@@ -1499,18 +1504,14 @@ def bn_act_maxpool(x, bn, pool):
     """pool(relu(bn(x))) for the ResNet stem (eval-mode BN, MaxPool2d(3, 2, 1)) in one HIP pass
     (frh_bn_act_maxpool) when nothing needs a gradient through it (the reference freezes the
     stem: frozen_stages >= 0); otherwise bn_act then the pool module."""
-    fused = (x.is_cuda and x.dtype == torch.float32 and not bn.training and x.is_contiguous()
-             and x.shape[3] % 8 == 0 and x.shape[3] >= 8
+    fused = (_f32_hip_4d(x) and _frozen_bn(bn) and x.is_contiguous() and x.shape[3] % 8 == 0 and x.shape[3] >= 8
              and (pool.kernel_size, pool.stride, pool.padding, pool.dilation) in ((3, 2, 1, 1), ((3, 3), (2, 2), (1, 1), (1, 1)))
-             and not pool.ceil_mode and not pool.return_indices
-             and not (torch.is_grad_enabled() and (x.requires_grad or (bn.weight is not None and bn.weight.requires_grad)
-                                                   or (bn.bias is not None and bn.bias.requires_grad))))
+             and not pool.ceil_mode and not pool.return_indices and not _needs_grad(x, bn.weight, bn.bias))
     if not fused:
         return pool(bn_act(x, bn))
     n, c, h, w = x.shape
     y = torch.empty(n, c, (h - 1) // 2 + 1, w // 2, dtype=torch.float32, device=x.device)
-    call('frh_bn_act_maxpool', ptr(x), ptr(y), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-         ptr(bn.running_var), float(bn.eps), n, c, h, w, stream_of(x))
+    call('frh_bn_act_maxpool', ptr(x), ptr(y), *_bn_args(bn), n, c, h, w, stream_of(x))
     return y
 
 

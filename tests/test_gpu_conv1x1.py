@@ -123,6 +123,52 @@ def test_entry_refuses_what_it_cannot_run(dev):
                   _lib.stream_of(x))
 
 
+def test_entry_refuses_partial_overlap(dev):
+    """y must not share a byte with skip or x (n = 1, cin = 16, cout = 64, hw = 4, the smallest
+    shape the entry takes): refused by range, not by pointer equality, and before any launch, so
+    the buffer keeps its contents."""
+    from frcnn_amd import _lib
+    buf = torch.arange(1.0, 385.0, device=dev)
+    before = buf.clone()
+    w = torch.ones(64, 16, device=dev)
+    x = torch.ones(1, 16, 2, 2, device=dev)
+    y = buf[:256]
+    p = _lib.ptr
+
+    def run(x, skip):
+        _lib.call('frh_conv1x1_bn_act', p(x), p(w), p(skip) if skip is not None else None, p(y), None, None, None,
+                  None, EPS, 1, 16, 64, 4, 0, _lib.stream_of(buf))
+    with pytest.raises(RuntimeError, match='alias'):
+        run(x, buf[64:320])      # skip starts 256 bytes into y
+    with pytest.raises(RuntimeError, match='alias'):
+        run(buf[224:288], None)  # x starts in y's last 128 bytes
+    torch.cuda.synchronize()
+    assert torch.equal(buf, before)
+
+
+def test_bn_without_running_statistics_takes_the_modules(dev, monkeypatch):
+    """An eval-mode BatchNorm2d(track_running_stats=False) normalises with the batch's statistics:
+    ops.conv1x1_bn_act and ops.bn_act call no library entry for it (read off ops.call) and return
+    relu(bn(conv(x))), to test_dispatch's tolerance for two calls of one MIOpen conv."""
+    from frcnn_amd import ops
+    torch.manual_seed(7)
+    conv = torch.nn.Conv2d(16, 64, 1, bias=False).to(dev)
+    bn = torch.nn.BatchNorm2d(64, track_running_stats=False).to(dev).eval()
+    x = torch.randn(1, 16, 2, 2, device=dev)
+    names = []
+    real_call = ops.call
+    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    with torch.no_grad():
+        ref = torch.relu(bn(conv(x)))
+        assert not ops.conv1x1_fused_ok(conv, bn, x)
+        got = ops.conv1x1_bn_act(conv, bn, x)
+        got_bn = ops.bn_act(conv(x), bn)
+    assert [n for n in names if n.startswith('frh_')] == []
+    tol = dict(rtol=1e-3, atol=1e-3 * float(ref.abs().max()))
+    torch.testing.assert_close(got, ref, **tol)
+    torch.testing.assert_close(got_bn, ref, **tol)
+
+
 def _conv_bn(dev, cin, cout, seed, **kw):
     torch.manual_seed(seed)
     conv = torch.nn.Conv2d(cin, cout, 1, bias=kw.pop('bias', False), **kw).to(dev)
