@@ -507,6 +507,26 @@ int32_t frh_atss_assign(int32_t batch, int32_t num_levels, const int32_t* grid_h
                         int32_t topk, int64_t* cls, float* reg, float* ctr, void* workspace,
                         size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- a17 FCOS scale-range targets
+ * Replaces FCOSHead.single_image_targets (lib/heads/fcos_head.py:371-416) with utils.sort_bbox
+ * (lib/utils.py:362-366), bbox2ltrb (:78-87), positive_ltrb (:51-53), centerness (:56-59) and
+ * paint_value (:90-94), for all images of a batch in ONE launch.  Levels, gts, num_gts,
+ * gt_labels, img_hw and the three outputs exactly as frh_atss_assign takes and writes them;
+ * scale_thr [num_levels + 1] (host): the head's level_scale_thr.  For cell (y, x) of level l with
+ * centre (x*stride + stride/2, y*stride + stride/2), gt g matches when its four ltrb distances
+ * are > 0 and scale_thr[l] <= max(ltrb) < scale_thr[l+1]; the cell's owner is the matching gt of
+ * smallest area (x2-x1+1)*(y2-y1+1), the largest index among equal areas -- the gt the reference,
+ * painting in descending-area order behind a stable sort, paints last.  The owner writes cls =
+ * its label and reg = its ltrb (also outside the painted image area, as the reference does) and,
+ * where the label is > 0, ctr = centerness(ltrb + 1e-6).  All f32 in the reference's operation
+ * order: bit-exact.  num_gts[b] is clamped to [0, max_gts]; max_gts == 0 is legal (background
+ * only).  No workspace. */
+int32_t frh_fcos_assign(int32_t batch, int32_t num_levels, const int32_t* grid_hw,
+                        const float* strides, const float* scale_thr, const float* gts,
+                        int64_t gt_seg_stride, const int32_t* num_gts, const int64_t* gt_labels,
+                        int32_t max_gts, const int32_t* img_hw, int64_t* cls, float* reg, float* ctr,
+                        void* stream);
+
 /* ---------------------------------------------------------------- backbone epilogue
  * Frozen BatchNorm (+ residual) (+ ReLU) of the reference ResNet's bottlenecks
  * (lib/backbones.py:69-76 keeps every BN in eval mode; torchvision Bottleneck.forward):
@@ -785,6 +805,38 @@ int32_t frh_gfl_loss_bwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cl
                          float bbox_weight, float dfl_avg_factor, const float* g, const float* fwd_out,
                          float* grad_cls, int64_t gc_sk, int64_t gc_si, float* grad_reg, int64_t gr_sc,
                          int64_t gr_si, void* stream);
+/* f1c: the three losses of the FCOS head without GFL (FCOSHead.calc_loss's last arm,
+ * fcos_head.py:419-515, which plain FCOS and ATSS-without-GFL both take; sigmoid_focal_loss
+ * lib/losses.py:33-61, giou_loss :13-30, CrossEntropyLoss(use_sigmoid=True) on one channel
+ * :144-147) of one batch in ONE launch, straight from the un-indexed head outputs: class logit
+ * (k, i) at cls[k*cls_sk + i*cls_si] (k < c), ltrb prediction of side s (the head's exp output) at
+ * reg[s*reg_ss + i*reg_si], centerness logit at ctr[i*ctr_si]; label [m] int64 (-1 ignored, 0
+ * negative, > 0 the class), ltrb [m, 4] f32 pixels (16-byte aligned), ctr_t [m] f32.
+ *   focal: every position with label >= 0 and every class k, the element frh_cls_loss_fwd kind 0
+ *     sums (target label == k+1), * cls_weight / num_pos;
+ *   box: positives (label > 0, counted on the device): y_s = (ltrb_s - reg_mean) / reg_std,
+ *     giou_loss of (-p_l, -p_t, p_r, p_b) against (-y_l, -y_t, y_r, y_b), * ctr_t, summed,
+ *     * bbox_weight / num_pos;
+ *   centerness: positives, bce_with_logits(ctr, ctr_t) summed, * ctr_weight / num_pos.
+ * out[4] = {cls_loss, bbox_loss, ctr_loss, (float)num_pos}.  DIVERGENCE: with no positive the
+ * sums are divided by max(num_pos, 1); the reference divides by zero.  status / workspace /
+ * determinism as frh_gfl_loss_fwd.  Backward writes d(g[0]*cls_loss + g[1]*bbox_loss +
+ * g[2]*ctr_loss) / d(cls, reg, ctr): g [3] and fwd_out are device memory; every element of the
+ * three gradients is written exactly once (0 at ignored / non-positive positions); the targets
+ * are constants; a tie of GIoU's min / max gives each operand a half, as torch does. */
+int32_t frh_fcos_loss_fwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cls_si, const float* reg,
+                          int64_t reg_ss, int64_t reg_si, const float* ctr, int64_t ctr_si,
+                          const int64_t* label, const float* ltrb, const float* ctr_t, int64_t m,
+                          float reg_mean, float reg_std, float alpha, float gamma, float cls_weight,
+                          float bbox_weight, float ctr_weight, const int32_t* status, float* out,
+                          void* workspace, size_t ws_bytes, void* stream);
+int32_t frh_fcos_loss_bwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cls_si, const float* reg,
+                          int64_t reg_ss, int64_t reg_si, const float* ctr, int64_t ctr_si,
+                          const int64_t* label, const float* ltrb, const float* ctr_t, int64_t m,
+                          float reg_mean, float reg_std, float alpha, float gamma, float cls_weight,
+                          float bbox_weight, float ctr_weight, const float* g, const float* fwd_out,
+                          float* grad_cls, int64_t gc_sk, int64_t gc_si, float* grad_reg, int64_t gr_ss,
+                          int64_t gr_si, float* grad_ctr, int64_t gt_si, void* stream);
 /* The DFL ("integral") box decode of one level for a batch (FCOSHead.predict_single_image,
  * fcos_head.py:579-600 with ltrb2bbox :63-75 and utils.clamp_bbox, lib/utils.py:109-120):
  * reg [batch, 4*bins, h, w] f32 with element strides (sb, sc, sy, sx) -- any layout, channels-

@@ -21,20 +21,17 @@
 //                  atomicMax(g), then the owners write label / ltrb / centerness.
 #include <math.h>
 
-#include "common.h"
+#include "ltrb_common.h"
 
 namespace frh {
 
-constexpr int kAtssMaxLevels = 16;
+constexpr int kAtssMaxLevels = kLtrbMaxLevels;
 constexpr int kAtssMaxK = 16;
 constexpr int kAtssThreads = 256;
 
 struct AtssArgs {
-  int B, L, K, Gmax;
-  int64_t N;
-  int64_t off[kAtssMaxLevels + 1];
-  int gh[kAtssMaxLevels], gw[kAtssMaxLevels];
-  float stride[kAtssMaxLevels];
+  int B, K, Gmax;
+  LevelTable lv;  // ltrb_common.h
   const float* anchors;
   int64_t ald;
   const float* gts;
@@ -53,24 +50,14 @@ struct AtssArgs {
   int32_t* owner;  // [B][N]
 };
 
-__device__ __forceinline__ int level_of(const AtssArgs& a, int64_t c) {
-  int l = 0;
-  while (l + 1 < a.L && c >= a.off[l + 1]) ++l;
-  return l;
-}
-
 __global__ void atss_fill_kernel(AtssArgs a) {
   const int b = blockIdx.y;
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= a.N) return;
-  const int l = level_of(a, c);
-  const int64_t i = c - a.off[l];
-  const int y = (int)(i / a.gw[l]), x = (int)(i - (int64_t)y * a.gw[l]);
-  // paint_value: [0, 0, img_w, img_h] * (1 / stride) in f32, round half-even, inclusive slice
-  const float sc = (float)(1.0 / (double)a.stride[l]);
-  const int x2 = (int)rintf((float)a.img_hw[2 * b + 1] * sc), y2 = (int)rintf((float)a.img_hw[2 * b] * sc);
-  const bool in = y <= y2 && x <= x2;
-  const int64_t o = (int64_t)b * a.N + c;
+  if (c >= a.lv.N) return;
+  int y, x;
+  const int l = cell_yx(a.lv, c, &y, &x);
+  const bool in = painted(a.img_hw, b, a.lv.stride[l], y, x);
+  const int64_t o = (int64_t)b * a.lv.N + c;
   a.cls[o] = in ? 0 : -1;
   a.ctr[o] = in ? 0.0f : -1.0f;
   reinterpret_cast<float4*>(a.reg)[o] = make_float4(-1.0f, -1.0f, -1.0f, -1.0f);
@@ -112,8 +99,8 @@ __global__ void __launch_bounds__(kAtssThreads) atss_topk_kernel(AtssArgs a) {
   gt_box(a, b, g, bx);
   // topk_by_center: centre_of(anchor) - centre_of(gt), L2 norm, k smallest
   const float bcx = (bx[2] + bx[0]) / 2.0f, bcy = (bx[3] + bx[1]) / 2.0f;
-  const int64_t hw = (int64_t)a.gh[l] * a.gw[l];
-  const int64_t c0 = a.off[l];
+  const int64_t hw = (int64_t)a.lv.gh[l] * a.lv.gw[l];
+  const int64_t c0 = a.lv.off[l];
   const float* A = a.anchors;
   const int64_t ld = a.ald;
   uint64_t best[kAtssMaxK];
@@ -149,7 +136,7 @@ __global__ void __launch_bounds__(kAtssThreads) atss_topk_kernel(AtssArgs a) {
     }
   }
   __syncthreads();
-  const int LK = a.L * a.K;
+  const int LK = a.lv.L * a.K;
   const int64_t base = ((int64_t)b * a.Gmax + g) * LK + (int64_t)l * a.K;
   for (int j = threadIdx.x; j < a.K; j += blockDim.x) {
     const uint64_t key = s_top[j];
@@ -165,21 +152,15 @@ __global__ void __launch_bounds__(kAtssThreads) atss_topk_kernel(AtssArgs a) {
 }
 
 __device__ __forceinline__ void cell_ltrb(const AtssArgs& a, int64_t c, const float* bx, float* lt) {
-  const int l = level_of(a, c);
-  const int64_t i = c - a.off[l];
-  const int y = (int)(i / a.gw[l]), x = (int)(i - (int64_t)y * a.gw[l]);
-  const float s = a.stride[l];
-  const float cx = (float)x * s + s / 2.0f, cy = (float)y * s + s / 2.0f;
-  lt[0] = cx - bx[0];
-  lt[1] = cy - bx[1];
-  lt[2] = bx[2] - cx;
-  lt[3] = bx[3] - cy;
+  int y, x;
+  const int l = cell_yx(a.lv, c, &y, &x);
+  center_ltrb(a.lv.stride[l], y, x, bx, lt);
 }
 
 __global__ void __launch_bounds__(kAtssThreads) atss_resolve_kernel(AtssArgs a) {
   const int b = blockIdx.x;
   const int G = a.ngt[b];
-  const int LK = a.L * a.K;
+  const int LK = a.lv.L * a.K;
   const int64_t cb = (int64_t)b * a.Gmax * LK;
   const int32_t* cand = a.cand + cb;
   const float* ciou = a.ciou + cb;
@@ -216,7 +197,7 @@ __global__ void __launch_bounds__(kAtssThreads) atss_resolve_kernel(AtssArgs a) 
     valid[e] = v;
   }
   __syncthreads();
-  int32_t* owner = a.owner + (int64_t)b * a.N;
+  int32_t* owner = a.owner + (int64_t)b * a.lv.N;
   for (int e = threadIdx.x; e < G * LK; e += blockDim.x) {
     if (!valid[e]) continue;
     const int g = e / LK, j = e - g * LK, lb = (j / a.K) * a.K;
@@ -239,12 +220,10 @@ __global__ void __launch_bounds__(kAtssThreads) atss_resolve_kernel(AtssArgs a) 
     float bx[4], lt[4];
     gt_box(a, b, g, bx);
     cell_ltrb(a, c, bx, lt);
-    const int64_t o = (int64_t)b * a.N + c;
+    const int64_t o = (int64_t)b * a.lv.N + c;
     a.cls[o] = a.labels[(int64_t)b * a.Gmax + g];
     reinterpret_cast<float4*>(a.reg)[o] = make_float4(lt[0], lt[1], lt[2], lt[3]);
-    // centerness on ltrb + 1e-6
-    const float l = lt[0] + 1e-6f, t = lt[1] + 1e-6f, r = lt[2] + 1e-6f, bb = lt[3] + 1e-6f;
-    a.ctr[o] = sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(t, bb) / fmaxf(t, bb)));
+    a.ctr[o] = ltrb_centerness(lt);
   }
 }
 
@@ -294,23 +273,12 @@ extern "C" int32_t frh_atss_assign(int32_t batch, int32_t num_levels, const int3
   if (batch == 0) return FRH_OK;
   AtssArgs a{};
   a.B = batch;
-  a.L = num_levels;
   a.K = topk;
   a.Gmax = max_gts;
-  int64_t n = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    FRH_REQUIRE(grid_hw[2 * l] >= 1 && grid_hw[2 * l + 1] >= 1, "empty grid at level %d", l);
-    FRH_REQUIRE(strides[l] > 0.0f, "stride must be positive");
-    a.off[l] = n;
-    a.gh[l] = grid_hw[2 * l];
-    a.gw[l] = grid_hw[2 * l + 1];
-    a.stride[l] = strides[l];
-    n += (int64_t)a.gh[l] * a.gw[l];
-  }
-  a.off[num_levels] = n;
-  FRH_REQUIRE(n < ((int64_t)1 << 31), "too many cells");
+  const int32_t lst = set_levels(&a.lv, num_levels, grid_hw, strides);
+  if (lst != FRH_OK) return lst;
+  const int64_t n = a.lv.N;
   FRH_REQUIRE(anchor_ld >= n, "anchor_ld %lld < cells %lld", (long long)anchor_ld, (long long)n);
-  a.N = n;
   FRH_REQUIRE(anchors && num_gts && img_hw && cls && reg && ctr, "null pointer argument");
   FRH_REQUIRE(max_gts == 0 || (gts && gt_labels), "null gt pointer");
   const AtssLayout w = atss_layout(batch, max_gts, num_levels, topk, n);

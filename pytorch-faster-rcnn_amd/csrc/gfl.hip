@@ -41,6 +41,7 @@
 // DFL loss is divided by the constant 4 and not by num_pos, so y's own f32 rounding would show
 // in its gradient.  At left == bins-1 the reference indexes past the last bin and raises; here the
 // right-hand DFL term is dropped and no such lane exists to be read (include/frcnn_amd.h).
+#include "giou.h"
 #include "loss_common.h"
 
 #include <math.h>
@@ -80,14 +81,6 @@ __device__ __forceinline__ float side_sum(float v) {
 }
 
 __device__ __forceinline__ float qfl_pow(float d, float beta) { return beta == 2.0f ? d * d : powf(d, beta); }
-
-// derivative weights of torch.max / torch.min of two operands with respect to the first (ties: half)
-__device__ __forceinline__ float dmax_a(float a, float b) { return a > b ? 1.0f : (a == b ? 0.5f : 0.0f); }
-__device__ __forceinline__ float dmin_a(float a, float b) { return a < b ? 1.0f : (a == b ? 0.5f : 0.0f); }
-
-__device__ __forceinline__ float sel4(int s, float v0, float v1, float v2, float v3) {
-  return s == 0 ? v0 : (s == 1 ? v1 : (s == 2 ? v2 : v3));
-}
 
 struct PosEval {
   float w;      // max_k sigmoid(cls(k, j))                         (wave-uniform)
@@ -140,30 +133,12 @@ __device__ __forceinline__ PosEval eval_positive(const GflArgs& a, int64_t j, in
   const float y0 = __shfl(y, 0, kWave), y1 = __shfl(y, 1, kWave), y2 = __shfl(y, 2, kWave), y3 = __shfl(y, 3, kWave);
   const float a0 = 0.0f - l0, a1 = 0.0f - l1, a2 = 0.0f + l2, a3 = 0.0f + l3;
   const float b0 = 0.0f - y0, b1 = 0.0f - y1, b2 = 0.0f + y2, b3 = 0.0f + y3;
-  const float tl0 = fmaxf(a0, b0), tl1 = fmaxf(a1, b1), br0 = fminf(a2, b2), br1 = fminf(a3, b3);
-  const float iw = br0 - tl0, ih = br1 - tl1;
-  const float msk = (tl0 < br0 && tl1 < br1) ? 1.0f : 0.0f;
-  const float area_i = (iw * ih) * msk;
-  const float wa = a2 - a0, ha = a3 - a1;
-  const float area_a = wa * ha, area_b = (b2 - b0) * (b3 - b1);
-  const float area_u = (area_a + area_b) - area_i;
-  const float iou = area_i / area_u;
-  const float cw = fmaxf(a2, b2) - fminf(a0, b0), ch = fmaxf(a3, b3) - fminf(a1, b1);
-  const float area_c = cw * ch;
-  r.q = iou;
-  r.giou = 1.0f - (iou - (area_c - area_u) / area_c);
+  const Giou gv = giou_eval(a0, a1, a2, a3, b0, b1, b2, b3);  // giou.h
+  r.q = gv.iou;
+  r.giou = gv.loss;
   r.g_dfl = r.g_box = 0.0f;
   if constexpr (kGrad) {
-    // d giou_loss / d a_i = -d iou - d (area_u / area_c)
-    const float dA = sel4(side, -ha, -wa, ha, wa);
-    const float dI = sel4(side, -(msk * ih) * dmax_a(a0, b0), -(msk * iw) * dmax_a(a1, b1),
-                          (msk * ih) * dmin_a(a2, b2), (msk * iw) * dmin_a(a3, b3));
-    const float dC = sel4(side, -ch * dmin_a(a0, b0), -cw * dmin_a(a1, b1), ch * dmax_a(a2, b2),
-                          cw * dmax_a(a3, b3));
-    const float dU = dA - dI;
-    const float diou = (dI * area_u - area_i * dU) / (area_u * area_u);
-    const float dratio = (dU * area_c - area_u * dC) / (area_c * area_c);
-    const float dbox = -diou - dratio;                // d giou_loss / d a_side
+    const float dbox = giou_dside(gv, side, a0, a1, a2, a3, b0, b1, b2, b3);  // d giou_loss / d a_side
     const float dlen = side < 2 ? -dbox : dbox;       // a = (-len_l, -len_t, len_r, len_b)
     r.g_box = act ? (p * (posb - len)) * dlen : 0.0f; // through the softmax expectation
     // d/dx_b of wl * logsm[left] + wr * logsm[left+1], d logsm[c] / d x_b = [b == c] - p_b
@@ -175,51 +150,12 @@ __device__ __forceinline__ PosEval eval_positive(const GflArgs& a, int64_t j, in
   return r;
 }
 
-__device__ __forceinline__ int block_sum_i(int v, int* scratch) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  if (lane_id() == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-  if (threadIdx.x == 0)
-    for (int j = 0; j < kLossThreads / kWave; ++j) t += scratch[j];
-  return t;
-}
-
 // The last workgroup to arrive sums the four partial arrays in a fixed order (losses.hip:
 // det_fan_in) and scales as the reference's modules do: (sum * loss_weight) / avg_factor in f32.
 __device__ void gfl_fan_in(float pc, float pd, float pb, int np, uint32_t* counter, float* partial,
                            const GflScale& o, float* out, const int32_t* status) {
-  __shared__ double s[kLossThreads];
-  __shared__ int last;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(partial + blockIdx.x, pc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + kMaxPartials + blockIdx.x, pd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + 2 * kMaxPartials + blockIdx.x, pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + 3 * kMaxPartials + blockIdx.x, (float)np, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);  // exact in f32: a workgroup counts fewer than 2^24
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = old == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
   double res[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float* p = partial + q * kMaxPartials;
-    double v = 0.0;
-    for (int j = threadIdx.x; j < (int)gridDim.x; j += kLossThreads)
-      v += (double)__hip_atomic_load(const_cast<float*>(p + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-      __syncthreads();
-    }
-    res[q] = s[0];
-    __syncthreads();
-  }
+  if (!fan_in4(pc, pd, pb, np, counter, partial, res)) return;  // loss_common.h
   if (threadIdx.x == 0) {
     const float npos = (float)res[3];
     const float d = fmaxf(npos, 1.0f);

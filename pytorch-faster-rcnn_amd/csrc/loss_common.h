@@ -1,6 +1,7 @@
-// Pieces the fused loss files share (losses.hip, gfl.hip): the launch shape, the workspace
-// layout behind frh_loss_workspace(), torch's BCE-with-logits / sigmoid forms, the block sum and
-// the status-word read.  Moved here from losses.hip unchanged.
+// Pieces the fused loss files share (losses.hip, gfl.hip, fcos.hip): the launch shape, the
+// workspace layout behind frh_loss_workspace(), torch's BCE-with-logits / sigmoid forms, the
+// focal element, the block sums, the four-sum arrival fan-in and the status-word read.  Moved
+// here from losses.hip and gfl.hip unchanged.
 #pragma once
 #include "common.h"
 
@@ -29,6 +30,78 @@ __device__ __forceinline__ float block_sum_f(float v, float* scratch) {
   if (lane_id() == 0) scratch[w] = v;
   __syncthreads();
   float t = 0.0f;
+  if (threadIdx.x == 0)
+    for (int j = 0; j < kLossThreads / kWave; ++j) t += scratch[j];
+  return t;
+}
+
+// sigmoid_focal_loss element (losses.py:48-61) and its derivative (from losses.hip, shared with
+// fcos.hip so both evaluate the same element).
+__device__ __forceinline__ float focal_elem(float x, float t, float alpha, float gamma, float* dx) {
+  float p = sigmoidf(x);
+  float pt = p * t + (1.0f - p) * (1.0f - t);
+  float at = alpha * t + (1.0f - alpha) * (1.0f - t);
+  float q = 1.0f - pt;
+  float qg = powf(q, gamma);
+  float w = at * qg;
+  float bce = bce_logits(x, t);
+  if (dx) {
+    // d/dx [bce * at * q^gamma] = (p - t) * w + bce * at * gamma * q^(gamma-1) * (-dpt/dx),
+    // dpt/dx = p (1 - p) (2t - 1)
+    float dq = gamma * powf(q, gamma - 1.0f);
+    float dpt = p * (1.0f - p) * (2.0f * t - 1.0f);
+    *dx = (p - t) * w - bce * at * dq * dpt;
+  }
+  return bce * w;
+}
+
+// The arrival-counter fan-in of a forward with three sums and a positive count (from gfl.hip's
+// gfl_fan_in, shared with fcos.hip).  Thread 0 holds the workgroup's partials; every workgroup
+// stores them write-through, drains and adds to the counter; the workgroup whose add returns
+// gridDim.x - 1 gets true (in all its threads) and, in res, the four sums over the workgroups in
+// a fixed order (double: one slot per thread, then a tree).  Its thread 0 writes the outputs and
+// then resets the counter.  partial: kLossPartialArrays arrays of kMaxPartials floats.
+__device__ inline bool fan_in4(float p0, float p1, float p2, int np, uint32_t* counter, float* partial,
+                               double (&res)[4]) {
+  __shared__ double s[kLossThreads];
+  __shared__ int last;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(partial + blockIdx.x, p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + kMaxPartials + blockIdx.x, p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + 2 * kMaxPartials + blockIdx.x, p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + 3 * kMaxPartials + blockIdx.x, (float)np, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);  // exact in f32: a workgroup counts fewer than 2^24
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = old == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return false;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float* p = partial + q * kMaxPartials;
+    double v = 0.0;
+    for (int j = threadIdx.x; j < (int)gridDim.x; j += kLossThreads)
+      v += (double)__hip_atomic_load(const_cast<float*>(p + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+      __syncthreads();
+    }
+    res[q] = s[0];
+    __syncthreads();
+  }
+  return true;
+}
+
+// sum of an int over the workgroup, in thread 0 (from gfl.hip)
+__device__ __forceinline__ int block_sum_i(int v, int* scratch) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  if (lane_id() == 0) scratch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
   if (threadIdx.x == 0)
     for (int j = 0; j < kLossThreads / kWave; ++j) t += scratch[j];
   return t;

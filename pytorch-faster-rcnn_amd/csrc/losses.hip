@@ -66,24 +66,7 @@ __device__ __forceinline__ int64_t label_at(const ClsArgs& a, int64_t i) {
 // (the reference's sampled targets never carry such labels)
 __device__ __forceinline__ bool ignored(const ClsArgs& a, int64_t i) { return !a.tfloat && label_at(a, i) < 0; }
 
-// sigmoid_focal_loss element (losses.py:48-61) and its derivative.
-__device__ __forceinline__ float focal_elem(float x, float t, float alpha, float gamma, float* dx) {
-  float p = sigmoidf(x);
-  float pt = p * t + (1.0f - p) * (1.0f - t);
-  float at = alpha * t + (1.0f - alpha) * (1.0f - t);
-  float q = 1.0f - pt;
-  float qg = powf(q, gamma);
-  float w = at * qg;
-  float bce = bce_logits(x, t);
-  if (dx) {
-    // d/dx [bce * at * q^gamma] = (p - t) * w + bce * at * gamma * q^(gamma-1) * (-dpt/dx),
-    // dpt/dx = p (1 - p) (2t - 1)
-    float dq = gamma * powf(q, gamma - 1.0f);
-    float dpt = p * (1.0f - p) * (2.0f * t - 1.0f);
-    *dx = (p - t) * w - bce * at * dq * dpt;
-  }
-  return bce * w;
-}
+// focal_elem: the sigmoid_focal_loss element and its derivative, loss_common.h
 
 __device__ __forceinline__ void elem_index(const ClsArgs& a, int64_t e, int64_t* i, int64_t* k) {
   if (a.i_fast) {

@@ -152,6 +152,13 @@ SIGNATURES = {
                                c_f32, c_f32, c_vp, c_vp]),
     'frh_atss_assign': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32,
                                 c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'frh_fcos_assign': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), P(c_f32), c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
+                                c_vp, c_vp, c_vp, c_vp]),
+    'frh_fcos_loss_fwd': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                  c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_size, c_vp]),
+    'frh_fcos_loss_bwd': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                  c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                  c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
 }
 
 ABI_VERSION = 3

@@ -1,13 +1,15 @@
-"""FCOSHead (reference lib/heads/fcos_head.py) with the ATSS target path on HIP.
+"""FCOSHead (reference lib/heads/fcos_head.py) with both target paths and the head losses on HIP.
 
 ATSS targets (fcos_head.py:283-368) for every image of the batch
 come from one `ops.atss_assign` call (frh_atss_assign: fill, per-(gt, level)
-top-k, per-image resolve).  The GFL head (QFL + DFL + GIoU, :419-515) computes its
-three losses in one `ops.gfl_losses` launch (frh_gfl_loss_fwd / _bwd) and decodes its
-boxes with `ops.dfl_decode` (frh_dfl_decode, :579-600).  The plain FCOS scale-range
-targets (fcos_head.py:371-420), the other loss combinations (focal / GIoU /
-centerness, QFL alone, DFL alone) and the rest of inference (:566-627) are
-PyTorch-ROCm tensor code around them.
+top-k, per-image resolve); the plain FCOS scale-range targets (:371-416) from one
+`ops.fcos_assign` launch (frh_fcos_assign).  The GFL head (QFL + DFL + GIoU, :419-515)
+computes its three losses in one `ops.gfl_losses` launch (frh_gfl_loss_fwd / _bwd) and
+decodes its boxes with `ops.dfl_decode` (frh_dfl_decode, :579-600); the head without GFL
+(focal + GIoU + centerness: plain FCOS and ATSS alike) computes its three in one
+`ops.fcos_losses` launch (frh_fcos_loss_fwd / _bwd).  The other loss combinations (QFL
+alone, DFL alone), CPU tensors and the rest of inference (:566-627) are PyTorch-ROCm
+tensor code around them.
 The LTRB helpers keep the reference's names and semantics.
 """
 import logging
@@ -236,11 +238,26 @@ class FCOSHead(ChannelsLastConvs):
                 self._split_levels(ctr[0], grids, 1))
 
     # ------------------------------------------------------------ plain FCOS targets
+    def targets_batched(self, grids, gt_bboxes, gt_labels, img_metas):
+        """Level-concatenated (cls [B, N] i64, reg [B, N, 4], ctr [B, N]) for the batch: the
+        scale-range assignment of every image in one launch (csrc/fcos.hip)."""
+        return ops.fcos_assign(grids, [float(s) for s in self.strides], list(gt_bboxes), list(gt_labels),
+                               [m['img_shape'][:2] for m in img_metas], self.level_scale_thr)
+
     def single_image_targets(self, cls_outs, reg_outs, ctr_outs, gt_bboxes, gt_labels, img_meta, train_cfg):
-        """fcos_head.py:371-420: scale-range assignment, larger gts first."""
+        """fcos_head.py:371-420: scale-range assignment, larger gts first.  Per-level ([H, W, 1]
+        labels, [H, W, 4] ltrb, [H, W, 1] centerness); for HIP tensors views of the batched call."""
+        grids = [tuple(x.shape[-2:]) for x in cls_outs]
+        if cls_outs[0].is_cuda:
+            cls, reg, ctr = self.targets_batched(grids, [gt_bboxes], [gt_labels], [img_meta])
+            return (self._split_levels(cls[0], grids, 1), self._split_levels(reg[0], grids, 4),
+                    self._split_levels(ctr[0], grids, 1))
+        return self.single_image_targets_torch(grids, gt_bboxes, gt_labels, img_meta)
+
+    def single_image_targets_torch(self, grids, gt_bboxes, gt_labels, img_meta):
+        """The reference's loop in torch ops, on the gts' device: what CPU tensors take."""
         gt_bboxes, gt_labels = utils.sort_bbox(gt_bboxes, labels=gt_labels, descending=True)
-        dev = cls_outs[0].device
-        grids = [x.shape[-2:] for x in cls_outs]
+        dev = gt_bboxes.device
         img_h, img_w = img_meta['img_shape'][:2]
         cls_tars = make_level_blanks(grids, 1, -1, torch.long, dev)
         reg_tars = make_level_blanks(grids, 4, -1, torch.float, dev)
@@ -278,6 +295,26 @@ class FCOSHead(ChannelsLastConvs):
                 cls_weight=self.loss_cls.loss_weight, dfl_weight=d.loss_weight,
                 bbox_weight=self.loss_bbox.loss_weight, dfl_avg_factor=4.0)
             return OrderedDict([('cls_loss', cls_loss), ('dfl_loss', dfl_loss), ('bbox_loss', bbox_loss)])
+        if not self.use_gfl and self.use_centerness and isinstance(self.loss_bbox, losses.GIoULoss) \
+                and isinstance(self.loss_cls, losses.FocalLoss) \
+                and isinstance(self.loss_centerness, losses.CrossEntropyLoss) and self.loss_centerness.use_sigmoid:
+            # plain FCOS and ATSS without GFL: focal, GIoU x centerness target and centerness BCE
+            # straight from the un-indexed flat tensors -- one HIP launch (csrc/fcos.hip, no host
+            # read of the positive count), or its torch restatement for CPU tensors
+            if self.reg_mean > 0:
+                raise AssertionError('reg_mean must be <= 0 without GFL')
+            fn = ops.fcos_losses if cls_outs.is_cuda else losses.fcos_head_losses_torch
+            cls_loss, bbox_loss, ctr_loss, _ = fn(
+                cls_outs, reg_outs, ctr_outs, cls_tars, reg_tars, ctr_tars, reg_mean=self.reg_mean,
+                reg_std=self.reg_std, alpha=self.loss_cls.alpha, gamma=self.loss_cls.gamma,
+                cls_weight=self.loss_cls.loss_weight, bbox_weight=self.loss_bbox.loss_weight,
+                ctr_weight=self.loss_centerness.loss_weight)
+            return OrderedDict([('cls_loss', cls_loss), ('ctr_loss', ctr_loss), ('bbox_loss', bbox_loss)])
+        return self.calc_loss_modules(cls_outs, reg_outs, ctr_outs, cls_tars, reg_tars, ctr_tars)
+
+    def calc_loss_modules(self, cls_outs, reg_outs, ctr_outs, cls_tars, reg_tars, ctr_tars):
+        """The reference's loss, module by module (a host read of the positive count and boolean
+        gathers): QFL alone and DFL alone take it."""
         chosen = cls_tars >= 0
         pos = cls_tars > 0
         num_pos = int(pos.sum())
@@ -342,6 +379,10 @@ class FCOSHead(ChannelsLastConvs):
         if self.use_atss:
             cls_t, reg_t, ctr_t = self.targets_atss_batched(grids, gt_bboxes, gt_labels, img_metas,
                                                             cls_outs[0].device)
+            return self.calc_loss_flat(flat_o(cls_outs), flat_o(reg_outs), flat_o(ctr_outs), cls_t.view(-1),
+                                       reg_t.view(-1, 4), ctr_t.view(-1))
+        if cls_outs[0].is_cuda:
+            cls_t, reg_t, ctr_t = self.targets_batched(grids, gt_bboxes, gt_labels, img_metas)
             return self.calc_loss_flat(flat_o(cls_outs), flat_o(reg_outs), flat_o(ctr_outs), cls_t.view(-1),
                                        reg_t.view(-1, 4), ctr_t.view(-1))
         tars = utils.unpack_multi_result(utils.multi_apply(

@@ -327,3 +327,35 @@ def gfl_head_losses_torch(cls_outs, reg_outs, labels, ltrb, bins, stride, reg_me
     tar[torch.arange(n, device=pred.device), labels[chosen]] = q_all[chosen]
     cls_loss = generalized_focal_loss(pred, tar[:, 1:], beta=beta).sum() * cls_weight / div
     return cls_loss, dfl_loss, bbox_loss, num_pos
+
+
+def fcos_head_losses_torch(cls_outs, reg_outs, ctr_outs, labels, ltrb, ctr_tars, reg_mean=0.0, reg_std=1.0,
+                           alpha=0.25, gamma=2.0, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0):
+    """The FCOS head's three losses without GFL (the last arm of the reference's FCOSHead.calc_loss,
+    fcos_head.py:419-515, with FocalLoss, GIoULoss and the one-channel sigmoid CrossEntropyLoss)
+    restated in torch ops, expression for expression: the numerics reference of ops.fcos_losses
+    (csrc/fcos.hip) and what FCOSHead runs for CPU tensors.  CPU (f32 / f64) or HIP tensors; no
+    ops call.
+
+    cls_outs [C, M] logits, reg_outs [4, M] ltrb predictions (the head's exp output), ctr_outs
+    [M] or [1, M] logits, labels [M] int64 (-1 ignored, 0 negative, > 0 the class), ltrb [M, 4]
+    pixels, ctr_tars [M]; positions ordered images outer, levels inner.  Returns (cls_loss,
+    bbox_loss, ctr_loss, num_pos [int64 0-d]).  With no positive the sums are divided by
+    max(num_pos, 1); the reference divides by zero there."""
+    chosen, pos = labels >= 0, labels > 0
+    num_pos = pos.sum()
+    div = num_pos.clamp(min=1).to(cls_outs.dtype)
+    pos_ctr_outs = ctr_outs.reshape(-1, 1)[pos, :]
+    pos_ctr_tars = ctr_tars[pos]
+    # CrossEntropyLoss with one channel (losses.py:144-147) takes label.view(-1, 1).float(): with
+    # f64 inputs the element is still formed in f32, in the reference and here
+    ctr_sum = F.binary_cross_entropy_with_logits(pos_ctr_outs, pos_ctr_tars.view(-1, 1).float(),
+                                                 reduction='none').sum()
+    ctr_loss = ctr_sum * ctr_weight / div.to(ctr_sum.dtype)
+    y4 = (ltrb[pos, :].t() - reg_mean) / reg_std                       # [4, m]
+    p4 = reg_outs[:, pos]
+    a = torch.stack([0.0 - p4[0], 0.0 - p4[1], 0.0 + p4[2], 0.0 + p4[3]])
+    b = torch.stack([0.0 - y4[0], 0.0 - y4[1], 0.0 + y4[2], 0.0 + y4[3]])
+    bbox_loss = (giou_loss(a, b) * pos_ctr_tars).sum() * bbox_weight / div
+    cls_loss = cls_weight * sigmoid_focal_loss(cls_outs[:, chosen].t(), labels[chosen], alpha, gamma) / div
+    return cls_loss, bbox_loss, ctr_loss, num_pos

@@ -1011,18 +1011,50 @@ def atss_assign(anchors, grid_sizes, strides, gt_list, label_list, img_shapes, t
     N = sum(int(h) * int(w) for h, w in grid_sizes)
     if anchors.shape[1] != N or anchors.stride(1) != 1:
         raise AssertionError('anchors must be a [4, N] row-contiguous tensor with one anchor per cell')
-    gts, gcnt, gmax = pack_boxes([g.float() for g in gt_list], dev)
-    labels = pack_labels(label_list, gmax, dev)
-    img_hw = device_ints([int(v) for s in img_shapes for v in s[:2]], dev)
-    cls = torch.empty(B, N, dtype=torch.int64, device=dev)
-    reg = torch.empty(B, N, 4, dtype=torch.float32, device=dev)
-    ctr = torch.empty(B, N, dtype=torch.float32, device=dev)
+    gts, gcnt, gmax, labels, img_hw = _pack_ltrb_gts(gt_list, label_list, img_shapes, dev)
+    cls, reg, ctr = _ltrb_targets(B, N, dev)
     ws_n = _lib.query('frh_atss_workspace', B, gmax, L, int(topk), N)
     ws = workspace(ws_n, dev)
     hw = i32_array([int(v) for g in grid_sizes for v in g])
     call('frh_atss_assign', B, L, hw, f32_array(strides), ptr(anchors), anchors.stride(0), ptr(gts), gts.stride(0),
          ptr(gcnt), ptr(labels), gmax, ptr(img_hw), int(topk), ptr(cls), ptr(reg), ptr(ctr), ptr(ws), ws_n,
          stream_of(cls))
+    return cls, reg, ctr
+
+
+def _pack_ltrb_gts(gt_list, label_list, img_shapes, dev):
+    """The gt arguments the two LTRB assigners share: boxes [B, 4, gmax], counts, gmax, labels
+    [B, gmax] i64 and img_hw [B, 2] on the device, without a synchronisation."""
+    gts, gcnt, gmax = pack_boxes([g.float() for g in gt_list], dev)
+    labels = pack_labels(label_list, gmax, dev)
+    img_hw = device_ints([int(v) for s in img_shapes for v in s[:2]], dev)
+    return gts, gcnt, gmax, labels, img_hw
+
+
+def _ltrb_targets(B, N, dev):
+    return (torch.empty(B, N, dtype=torch.int64, device=dev), torch.empty(B, N, 4, dtype=torch.float32, device=dev),
+            torch.empty(B, N, dtype=torch.float32, device=dev))
+
+
+def fcos_assign(grid_sizes, strides, gt_list, label_list, img_shapes, scale_thr):
+    """Batched FCOSHead.single_image_targets (fcos_head.py:371-416) in one launch (csrc/fcos.hip).
+    grid_sizes / strides: per level; gt_list: per image [4, G_i] on the HIP device; label_list:
+    per image [G_i]; img_shapes: per image (h, w); scale_thr: the head's level_scale_thr
+    (len(grid_sizes) + 1 bounds).  Returns cls i64 [B, N], reg f32 [B, N, 4] (ltrb), ctr f32 [B, N]
+    over the level-concatenated cells, as atss_assign does."""
+    _need_cuda(*gt_list)
+    if not gt_list:
+        raise AssertionError('fcos_assign: at least one image expected')
+    dev = gt_list[0].device
+    B, L = len(gt_list), len(grid_sizes)
+    if len(strides) != L or len(scale_thr) != L + 1 or len(label_list) != B or len(img_shapes) != B:
+        raise AssertionError('fcos_assign: a stride per level, one more threshold, a label list and a shape per image')
+    N = sum(int(h) * int(w) for h, w in grid_sizes)
+    gts, gcnt, gmax, labels, img_hw = _pack_ltrb_gts(gt_list, label_list, img_shapes, dev)
+    cls, reg, ctr = _ltrb_targets(B, N, dev)
+    hw = i32_array([int(v) for g in grid_sizes for v in g])
+    call('frh_fcos_assign', B, L, hw, f32_array(strides), f32_array(scale_thr), ptr(gts), gts.stride(0), ptr(gcnt),
+         ptr(labels), gmax, ptr(img_hw), ptr(cls), ptr(reg), ptr(ctr), stream_of(cls))
     return cls, reg, ctr
 
 
@@ -1783,6 +1815,67 @@ def gfl_losses(cls_outs, reg_outs, labels, ltrb, bins, stride, reg_mean=0.0, reg
     cfg = (int(bins), float(stride), float(reg_mean), float(reg_std), int(bool(norm_prob)), float(beta),
            float(cls_weight), float(dfl_weight), float(bbox_weight), float(dfl_avg_factor))
     return _GflLoss.apply(_f32(cls_outs), _f32(reg_outs), labels.contiguous(), _f32(ltrb).contiguous(), cfg)
+
+
+# ---------------------------------------------------------------- f1c: FCOS head losses (no GFL)
+class _FcosLoss(torch.autograd.Function):
+    """Focal / GIoU / centerness losses of the FCOS head in one launch (frh_fcos_loss_fwd), one
+    launch backward (frh_fcos_loss_bwd); the positive count and the upstream gradients stay on the
+    device."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, ctr, labels, ltrb, ctr_t, cfg):
+        out = torch.empty(4, dtype=torch.float32, device=cls.device)
+        ws = _loss_workspace(cls)
+        call('frh_fcos_loss_fwd', *_fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, cfg), ptr(status_word(cls.device)),
+             ptr(out), ptr(ws), ws.numel(), stream_of(cls))
+        ctx.save_for_backward(cls, reg, ctr, labels, ltrb, ctr_t, out)
+        ctx.cfg = cfg
+        num_pos = out[3].long()
+        ctx.mark_non_differentiable(num_pos)
+        return out[0], out[1], out[2], num_pos
+
+    @staticmethod
+    def backward(ctx, gc, gb, gt, _):
+        cls, reg, ctr, labels, ltrb, ctr_t, out = ctx.saved_tensors
+        g = _f32(torch.stack([gc, gb, gt])).contiguous()
+        gcls, greg, gctr = torch.empty_like(cls), torch.empty_like(reg), torch.empty_like(ctr)
+        call('frh_fcos_loss_bwd', *_fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, ctx.cfg), ptr(g), ptr(out),
+             ptr(gcls), gcls.stride(0), gcls.stride(1), ptr(greg), greg.stride(0), greg.stride(1), ptr(gctr),
+             gctr.stride(0), stream_of(cls))
+        return gcls, greg, gctr, None, None, None, None
+
+
+def _fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, cfg):
+    reg_mean, reg_std, alpha, gamma, wc, wb, wt = cfg
+    return (ptr(cls), cls.shape[0], cls.stride(0), cls.stride(1), ptr(reg), reg.stride(0), reg.stride(1), ptr(ctr),
+            ctr.stride(0), ptr(labels), ptr(ltrb), ptr(ctr_t), cls.shape[1], reg_mean, reg_std, alpha, gamma, wc, wb,
+            wt)
+
+
+def fcos_losses(cls_outs, reg_outs, ctr_outs, labels, ltrb, ctr_tars, reg_mean=0.0, reg_std=1.0, alpha=0.25,
+                gamma=2.0, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0):
+    """(cls_loss, bbox_loss, ctr_loss, num_pos) of the FCOS head without GFL (csrc/fcos.hip; the
+    arguments and semantics of losses.fcos_head_losses_torch): cls_outs [C, M] logits, reg_outs
+    [4, M] ltrb predictions (the head's exp output) and ctr_outs [M] (or [1, M]) logits, f32 in any
+    strides; labels [M] int64, ltrb [M, 4], ctr_tars [M].  The losses are 0-d tensors, num_pos a
+    0-d int64 device tensor; nothing is read back to the host."""
+    _need_cuda(cls_outs, reg_outs, ctr_outs, labels, ltrb, ctr_tars)
+    if cls_outs.dim() != 2 or reg_outs.dim() != 2 or reg_outs.shape[0] != 4:
+        raise AssertionError('fcos_losses: cls_outs [C, M] and reg_outs [4, M] expected')
+    m = cls_outs.shape[1]
+    if ctr_outs.dim() == 2 and ctr_outs.shape[0] == 1:
+        ctr_outs = ctr_outs[0]
+    if reg_outs.shape[1] != m or ctr_outs.shape != (m,):
+        raise AssertionError('fcos_losses: reg_outs [4, M] and ctr_outs [M] must match cls_outs')
+    if labels.shape != (m,) or ltrb.shape != (m, 4) or ctr_tars.shape != (m,):
+        raise AssertionError('fcos_losses: labels [M], ltrb [M, 4] and ctr_tars [M] must match the outputs')
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    cfg = (float(reg_mean), float(reg_std), float(alpha), float(gamma), float(cls_weight), float(bbox_weight),
+           float(ctr_weight))
+    return _FcosLoss.apply(_f32(cls_outs), _f32(reg_outs), _f32(ctr_outs), labels.contiguous(),
+                           _f32(ltrb).contiguous(), _f32(ctr_tars).contiguous(), cfg)
 
 
 def dfl_decode(reg, bins, stride, reg_std, reg_mean, cell, img_size):
