@@ -847,6 +847,52 @@ int32_t frh_dfl_decode(const float* reg, int32_t batch, int32_t bins, int32_t h,
                        int64_t sc, int64_t sy, int64_t sx, double stride, float reg_std, float reg_mean,
                        float cell, float img_h, float img_w, float* boxes, void* stream);
 
+/* ---- dense-head candidates: the one-stage heads' NMS input for all images x levels ------
+ * FCOSHead.predict_single_image (fcos_head.py:570-621) and AnchorHead.predict_single_image
+ * (anchor_head.py:207-250) up to their multiclass NMS, in one memset and four launches
+ * whatever num_imgs, num_levels and num_classes; no device-to-host copy, no in-launch wait
+ * between workgroups (no device status word).
+ * Segment (image b, level l) has n_l = A * H_l * W_l columns; column a*H*W + y*W + x reads
+ * class channel c*A + a and reg channel coord*A + a, as frh_rpn_proposals_strided.
+ * cls / reg / ctr_strides [L][4]: element strides (b, c, y, x) of each level (NCHW or
+ * channels-last, no copy).  ctr_ptrs (with ctr_strides and out_factor) may be NULL.
+ * mode:
+ *  FRH_DENSE_DELTA  param2bbox(anchor, reg, means, stds) clamped to img_hw (frh_param2bbox's
+ *                   arithmetic); anchors [4][anchor_ld] from frh_anchor_grid.  Every column is
+ *                   a candidate; after the decode a row is invalid when min_size > 0 and
+ *                   w + 1 < min_size or h + 1 < min_size.
+ *  FRH_DENSE_LTRB   A = 1; ltrb = reg * reg_std + reg_mean around the cell centre
+ *                   (x*s + s/2, y*s + s/2), s = cell_strides[l], clamped.  Only columns with
+ *                   w + 1 > min_size and h + 1 > min_size are candidates (dropped BEFORE the
+ *                   top-k); a segment with fewer than k_l of them ends in invalid rows.
+ *  FRH_DENSE_DFL    as LTRB with, per side, the softmax expectation over `bins` x dfl_stride
+ *                   (reg channel bin*4 + side, frh_dfl_decode's arithmetic with the bins summed
+ *                   in one fixed tree order for every layout).  bins*4 > 64: FRH_EUNSUPPORTED.
+ * Key of a column: max_c sigmoid(cls_c), times sigmoid(ctr) with centerness maps.  Per segment
+ * the k_l = min(pre_nms, n_l) (n_l when pre_nms <= 0) largest keys are taken, ties to the
+ * lowest column; a candidate whose key is exactly 0 is still a candidate.  k_l <= 16384.
+ * Outputs (caller-owned, cap = sum_l k_l, level l's rows at offset sum_{l'<l} k_l' of every
+ * image, in (key descending, column ascending) order): boxes [B, cap, 4] (16-byte aligned),
+ * scores [B, cap, C] (the sigmoid of every class channel), factor [B, cap] (sigmoid(ctr)),
+ * valid [B, cap] uint8, index [B, cap] int32 (the column within its level, -1 for invalid
+ * rows).  Invalid rows hold zeros.  img_hw [B*2] / min_size [B]: host arrays, B <= 64. */
+#define FRH_DENSE_DELTA 0
+#define FRH_DENSE_LTRB 1
+#define FRH_DENSE_DFL 2
+size_t frh_dense_candidates_workspace(int32_t num_imgs, int32_t num_levels, const int32_t* grid_hw,
+                                      int32_t num_anchors, int32_t pre_nms);
+int32_t frh_dense_candidates(int32_t num_imgs, int32_t num_levels, const float* const* cls_ptrs,
+                             const float* const* reg_ptrs, const float* const* ctr_ptrs,
+                             const int64_t* cls_strides, const int64_t* reg_strides,
+                             const int64_t* ctr_strides, const int32_t* grid_hw, int32_t num_anchors,
+                             int32_t num_classes, int32_t mode, const float* anchors, int64_t anchor_ld,
+                             const float* means, const float* stds, const float* cell_strides,
+                             int32_t bins, double dfl_stride, float reg_std, float reg_mean,
+                             const float* img_hw, const float* min_size, int32_t pre_nms,
+                             float* out_boxes, float* out_scores, float* out_factor, uint8_t* out_valid,
+                             int32_t* out_index, int64_t cap, void* workspace, size_t ws_bytes,
+                             void* stream);
+
 /* ---------------------------------------------------------------- f4: image pipeline
  * The train/test pipelines of configs/faster_rcnn_r50_fpn.py:120-139 (mmdet v1: Resize
  * keep_ratio -> RandomFlip -> Normalize -> Pad(size_divisor) -> DefaultFormatBundle ->

@@ -150,6 +150,11 @@ SIGNATURES = {
                                  c_i64, c_i64, c_vp]),
     'frh_dfl_decode': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_f64, c_f32, c_f32, c_f32,
                                c_f32, c_f32, c_vp, c_vp]),
+    'frh_dense_candidates_workspace': (c_size, [c_i32, c_i32, P(c_i32), c_i32, c_i32]),
+    'frh_dense_candidates': (c_i32, [c_i32, c_i32, P(c_vp), P(c_vp), P(c_vp), P(c_i64), P(c_i64), P(c_i64), P(c_i32),
+                                     c_i32, c_i32, c_i32, c_vp, c_i64, P(c_f32), P(c_f32), P(c_f32), c_i32, c_f64,
+                                     c_f32, c_f32, P(c_f32), P(c_f32), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                     c_vp, c_size, c_vp]),
     'frh_atss_assign': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32,
                                 c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     'frh_fcos_assign': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), P(c_f32), c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,

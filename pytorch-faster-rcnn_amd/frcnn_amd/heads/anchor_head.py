@@ -209,10 +209,40 @@ class AnchorHead(ChannelsLastConvs):
         return list(range(1, self.num_classes)), 0
 
     def predict_single_image(self, level_cls_outs, level_reg_outs, level_anchors, img_meta, test_cfg):
-        """anchor_head.py:207-262: per-level top-k, decode, min-size filter, multiclass NMS."""
+        """anchor_head.py:207-262: per-level top-k, decode, min-size filter, multiclass NMS (the
+        B = 1 case of the batched paths)."""
+        cls_b, reg_b = [c.unsqueeze(0) for c in level_cls_outs], [r.unsqueeze(0) for r in level_reg_outs]
+        if self._dense_ok(cls_b, reg_b, test_cfg):
+            flat = torch.cat([a.reshape(4, -1) for a in level_anchors], 1).contiguous()
+            return [x[0] for x in self._predict_dense(cls_b, reg_b, flat, [img_meta], test_cfg)]
         return [x[0] for x in self._predict_batch([self.image_candidates(level_cls_outs, level_reg_outs,
                                                                          level_anchors, img_meta, test_cfg)],
                                                   test_cfg)]
+
+    def _dense_ok(self, cls_outs, reg_outs, test_cfg):
+        """Whether ops.dense_candidates takes the batch: a sigmoid head, f32 maps on the HIP
+        device, at most 64 images and ops.DENSE_MAX_ROWS rows per level.  Softmax heads and
+        everything else keep the per-image torch candidates (image_candidates)."""
+        if not self.use_sigmoid:
+            return False
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in list(cls_outs) + list(reg_outs)):
+            return False
+        rows = ops.dense_candidates_rows([c.shape[-2:] for c in cls_outs], self.num_anchors, test_cfg.pre_nms)
+        return cls_outs[0].shape[0] <= 64 and len(cls_outs) <= 8 and max(rows) <= ops.DENSE_MAX_ROWS
+
+    def _predict_dense(self, cls_outs, reg_outs, flat_anchors, img_metas, test_cfg):
+        """anchor_head.py:207-262 for the batch: ONE ops.dense_candidates call (per-level top-k by
+        the best class score, decode, clamp and min-size mask of every image,
+        csrc/dense_candidates.hip), then ONE class-wise batched multiclass NMS over its rows."""
+        labels, adjust = self._nms_labels()
+        boxes, scores, _, valid, _ = ops.dense_candidates(
+            cls_outs, reg_outs, None, 'DELTA', [m['img_shape'][:2] for m in img_metas],
+            [m['scale_factor'] * test_cfg.min_bbox_size for m in img_metas], test_cfg.pre_nms,
+            num_anchors=self.num_anchors, anchors=flat_anchors, means=self.target_means, stds=self.target_stds)
+        res = ops.multiclass_nms_batched(boxes, scores, labels, test_cfg.nms_iou, test_cfg.min_score,
+                                         test_cfg.max_per_img, mode=test_cfg.get('nms_type', 'official'),
+                                         row_valid=valid)
+        return [[kb.t() for kb, _, _ in res], [ks for _, ks, _ in res], [kl + adjust for _, _, kl in res]]
 
     def _predict_batch(self, cands, test_cfg):
         """One class-wise batched multiclass NMS (csrc/mcnms.hip) over the images' candidates
@@ -237,6 +267,9 @@ class AnchorHead(ChannelsLastConvs):
         """anchor_head.py:264-289 batched over the images: per-image candidates (device
         ops, no sync), then ONE multiclass NMS launch sequence for all images."""
         grid_sizes = [tuple(c.shape[-2:]) for c in cls_outs]
+        if self._dense_ok(cls_outs, reg_outs, test_cfg):
+            return self._predict_dense(cls_outs, reg_outs, self._flat_anchors(grid_sizes, cls_outs[0].device),
+                                       list(img_metas), test_cfg)
         level_anchors = self.create_anchors(grid_sizes)
         cands = [self.image_candidates([c[i] for c in cls_outs], [r[i] for r in reg_outs], level_anchors, meta,
                                        test_cfg) for i, meta in enumerate(img_metas)]

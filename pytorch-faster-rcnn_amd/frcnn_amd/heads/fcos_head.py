@@ -7,9 +7,11 @@ top-k, per-image resolve); the plain FCOS scale-range targets (:371-416) from on
 computes its three losses in one `ops.gfl_losses` launch (frh_gfl_loss_fwd / _bwd) and
 decodes its boxes with `ops.dfl_decode` (frh_dfl_decode, :579-600); the head without GFL
 (focal + GIoU + centerness: plain FCOS and ATSS alike) computes its three in one
-`ops.fcos_losses` launch (frh_fcos_loss_fwd / _bwd).  The other loss combinations (QFL
-alone, DFL alone), CPU tensors and the rest of inference (:566-627) are PyTorch-ROCm
-tensor code around them.
+`ops.fcos_losses` launch (frh_fcos_loss_fwd / _bwd).  Inference (:566-627) builds the NMS
+input of the whole batch with one `ops.dense_candidates` call (frh_dense_candidates) and runs
+one batched multiclass NMS; the GFL head keeps its per-level decode until `dense_dfl` is set.
+The other loss combinations (QFL alone, DFL alone) and CPU tensors (image_candidates, also
+the tests' oracle) are PyTorch-ROCm tensor code around them.
 The LTRB helpers keep the reference's names and semantics.
 """
 import logging
@@ -433,10 +435,48 @@ class FCOSHead(ChannelsLastConvs):
         return bx, sc, ct
 
     def predict_single_image(self, cls_outs, reg_outs, ctr_outs, img_meta, test_cfg):
-        """fcos_head.py:566-627."""
-        out = self._predict_batch([self.image_candidates(cls_outs, reg_outs, ctr_outs, img_meta, test_cfg)],
-                                  test_cfg)
+        """fcos_head.py:566-627: the B = 1 case of the batched paths."""
+        lift = lambda xs: [x.unsqueeze(0) for x in xs]
+        cls_b, reg_b = lift(cls_outs), lift(reg_outs)
+        ctr_b = lift(ctr_outs) if self.use_centerness else None
+        if self._dense_ok(cls_b, reg_b, ctr_b, test_cfg):
+            out = self._predict_dense(cls_b, reg_b, ctr_b, [img_meta], test_cfg)
+        else:
+            out = self._predict_batch([self.image_candidates(cls_outs, reg_outs, ctr_outs, img_meta, test_cfg)],
+                                      test_cfg)
         return out[0][0], out[1][0], out[2][0]
+
+    # GFL keeps its per-level ops.dfl_decode candidates unless this is set: the fused selection's
+    # DFL mode is complete and tested, the switch of the default is left to its own change
+    dense_dfl = False
+
+    def _dense_ok(self, cls_outs, reg_outs, ctr_outs, test_cfg):
+        """Whether ops.dense_candidates takes the batch: f32 maps on the HIP device, a DFL head of
+        at most 16 bins (with dense_dfl set), at most 64 images and ops.DENSE_MAX_ROWS rows per
+        level.  Otherwise the per-image torch candidates (image_candidates) run."""
+        maps = list(cls_outs) + list(reg_outs) + (list(ctr_outs) if self.use_centerness else [])
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in maps):
+            return False
+        if self.use_dfl and (not self.dense_dfl or self.loss_dfl.cls_channels * 4 > 64):
+            return False
+        rows = ops.dense_candidates_rows([c.shape[-2:] for c in cls_outs], 1, test_cfg['pre_nms'])
+        return cls_outs[0].shape[0] <= 64 and len(cls_outs) <= 8 and max(rows) <= ops.DENSE_MAX_ROWS
+
+    def _predict_dense(self, cls_outs, reg_outs, ctr_outs, img_metas, test_cfg):
+        """fcos_head.py:570-627 for the batch: ONE ops.dense_candidates call (decode, clamp,
+        min-size filter and per-level top-k of every image, csrc/dense_candidates.hip), then
+        ONE class-wise batched multiclass NMS over its rows."""
+        dfl = dict(bins=self.loss_dfl.cls_channels, dfl_stride=self.loss_dfl.stride) if self.use_dfl else {}
+        boxes, scores, factor, valid, _ = ops.dense_candidates(
+            cls_outs, reg_outs, ctr_outs if self.use_centerness else None, 'DFL' if self.use_dfl else 'LTRB',
+            [m['img_shape'][:2] for m in img_metas],
+            [m['scale_factor'] * test_cfg['min_bbox_size'] for m in img_metas], test_cfg['pre_nms'],
+            strides=[float(s) for s in self.strides[:len(cls_outs)]], reg_std=self.reg_std, reg_mean=self.reg_mean,
+            **dfl)
+        res = ops.multiclass_nms_batched(boxes, scores, list(range(0, self.cls_channels)), test_cfg['nms_iou'],
+                                         test_cfg['min_score'], test_cfg['max_per_img'], factor,
+                                         mode=test_cfg.get('nms_type', 'official'), row_valid=valid)
+        return [[kb.t() for kb, _, _ in res], [ks for _, ks, _ in res], [kl + 1 for _, _, kl in res]]
 
     def _predict_batch(self, cands, test_cfg):
         """ONE class-wise batched multiclass NMS (csrc/mcnms.hip) over the images' candidates,
@@ -461,6 +501,8 @@ class FCOSHead(ChannelsLastConvs):
 
     def predict_bboxes(self, feats, img_metas, test_cfg):
         cls_outs, reg_outs, ctr_outs = self.forward(feats)
+        if self._dense_ok(cls_outs, reg_outs, ctr_outs, test_cfg):
+            return self._predict_dense(cls_outs, reg_outs, ctr_outs, list(img_metas), test_cfg)
         ctrs = utils.split_by_image(ctr_outs) if self.use_centerness else [None] * len(img_metas)
         cands = [self.image_candidates(c, r, t, m, test_cfg) for c, r, t, m in
                  zip(utils.split_by_image(cls_outs), utils.split_by_image(reg_outs), ctrs, list(img_metas))]

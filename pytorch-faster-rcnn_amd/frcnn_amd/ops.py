@@ -1892,3 +1892,60 @@ def dfl_decode(reg, bins, stride, reg_std, reg_mean, cell, img_size):
          float(stride), float(reg_std), float(reg_mean), float(cell), float(img_size[0]), float(img_size[1]), ptr(out),
          stream_of(reg))
     return out
+
+
+# ---------------------------------------------------------------- dense-head candidates
+DENSE_MODES = {'DELTA': 0, 'LTRB': 1, 'DFL': 2}
+DENSE_MAX_ROWS = 16384  # rows of one level the gather launch orders in LDS
+
+
+def dense_candidates_rows(grid_sizes, num_anchors, pre_nms):
+    """k_l = min(pre_nms, n_l) (n_l when pre_nms <= 0) of every level."""
+    ns = [num_anchors * int(h) * int(w) for h, w in grid_sizes]
+    return [min(int(pre_nms), n) if pre_nms > 0 else n for n in ns]
+
+
+def dense_candidates(cls_outs, reg_outs, ctr_outs, mode, img_hw, min_sizes, pre_nms, num_anchors=1, anchors=None,
+                     means=None, stds=None, strides=None, bins=0, dfl_stride=1.0, reg_std=1.0, reg_mean=0.0):
+    """The one-stage heads' NMS input for all images x levels (frh_dense_candidates;
+    fcos_head.py:570-621, anchor_head.py:207-250): one memset and four launches, no host sync.
+
+    cls_outs / reg_outs / ctr_outs (or None): per-level [B, C*A, H, W] / [B, 4*A | 4*bins, H, W] /
+    [B, 1, H, W] f32 maps of any layout.  mode 'DELTA' (anchors [4, N], means, stds), 'LTRB' or
+    'DFL' (strides per level, reg_std, reg_mean; bins, dfl_stride).  img_hw [(h, w)] and
+    min_sizes per image.  Returns (boxes [B, cap, 4], scores [B, cap, C], factor [B, cap] or
+    None, valid bool [B, cap], index int32 [B, cap]) with cap = sum of the levels' k_l, rows in
+    (key descending, column ascending) order per level, invalid rows zero with index -1."""
+    ctrs = list(ctr_outs) if ctr_outs is not None else None
+    _need_cuda(*cls_outs)
+    _need_cuda(*reg_outs)
+    if ctrs is not None:
+        _need_cuda(*ctrs)
+    if mode not in DENSE_MODES:
+        raise AssertionError('unknown mode {}'.format(mode))
+    for t in list(cls_outs) + list(reg_outs) + (ctrs or []):
+        if t.dtype != torch.float32 or t.dim() != 4:
+            raise AssertionError('dense_candidates: f32 [B, C, H, W] maps expected')
+    B, L = cls_outs[0].shape[0], len(cls_outs)
+    A = int(num_anchors)
+    C = cls_outs[0].shape[1] // A
+    dev = cls_outs[0].device
+    grids = [(c.shape[2], c.shape[3]) for c in cls_outs]
+    grid_a = i32_array([v for g in grids for v in g])
+    cap = sum(dense_candidates_rows(grids, A, pre_nms))
+    boxes = torch.empty(B, cap, 4, dtype=torch.float32, device=dev)
+    scores = torch.empty(B, cap, C, dtype=torch.float32, device=dev)
+    factor = torch.empty(B, cap, dtype=torch.float32, device=dev) if ctrs is not None else None
+    valid = torch.empty(B, cap, dtype=torch.uint8, device=dev)
+    index = torch.empty(B, cap, dtype=torch.int32, device=dev)
+    ws = workspace(_lib.query('frh_dense_candidates_workspace', B, L, grid_a, A, int(pre_nms)), dev)
+    strides_of = lambda ts: i64_array([v for t in ts for v in t.stride()])
+    call('frh_dense_candidates', B, L, ptr_array(cls_outs), ptr_array(reg_outs),
+         ptr_array(ctrs) if ctrs is not None else None, strides_of(cls_outs), strides_of(reg_outs),
+         strides_of(ctrs) if ctrs is not None else None, grid_a, A, C, DENSE_MODES[mode],
+         ptr(anchors), anchors.stride(0) if anchors is not None else 0,
+         f32_array(means) if means is not None else None, f32_array(stds) if stds is not None else None,
+         f32_array(strides) if strides is not None else None, int(bins), float(dfl_stride), float(reg_std),
+         float(reg_mean), f32_array([v for hw in img_hw for v in hw[:2]]), f32_array(min_sizes), int(pre_nms),
+         ptr(boxes), ptr(scores), ptr(factor), ptr(valid), ptr(index), cap, ptr(ws), ws.numel(), stream_of(boxes))
+    return boxes, scores, factor, valid.view(torch.bool), index
