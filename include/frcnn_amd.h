@@ -527,6 +527,32 @@ int32_t frh_fcos_assign(int32_t batch, int32_t num_levels, const int32_t* grid_h
                         int32_t max_gts, const int32_t* img_hw, int64_t* cls, float* reg, float* ctr,
                         void* stream);
 
+/* ---------------------------------------------------------------- a18 Guided Anchoring targets
+ * Replaces GuidedAnchor.loc_target_single_image (lib/heads/guided_head.py:342-397) and the
+ * painting of shape_target_single_image_v2 (:195-231), with paint_value / paint_bbox (:23-39) and
+ * region.inside_grid_mask (lib/region.py:10-16), for all images of a batch in ONE launch.
+ * Levels, gts, num_gts and img_hw exactly as frh_fcos_assign takes them; gt_levels [batch,
+ * max_gts] i32: the level of each gt (region.map_gt2level, computed by the caller).  The region
+ * of gt (x1, y1, x2, y2) at ratio r on a level of stride s is, in f32, w = (x2 - x1 + 1) * r,
+ * cx = (x2 + x1) / 2 (h, cy likewise), (cx - w/2, cy - h/2, cx + w/2, cy + h/2) * (1 / s) rounded
+ * half to even; it covers cell (y, x) when rx1 <= x <= rx2 and ry1 <= y <= ry2.  Per cell of
+ * level l over the level-concatenated cells (N in all):
+ *   loc [batch, N] i64: 1 if a gt of level l has its center_ratio region over the cell; else -1
+ *     if a gt with |level - l| <= 1 has its ignore_ratio region over it; else 0 if y <
+ *     min(H_l, int(img_h / s) + 1) and x < min(W_l, int(img_w / s) + 1); else -1.
+ *   shape_mask [batch, N] i64 / shape_box [batch, N, 4] f32 (16-byte aligned): 1 and the box of
+ *     the highest-index gt of level l whose shape_center_ratio region covers the cell; 0 and
+ *     zeros elsewhere.
+ * This is what the reference's three painting passes leave behind, bit for bit, PROVIDED every
+ * gt coordinate is >= 0: a negative rounded edge is a negative slice index there and wraps
+ * around the map, which is not reproduced.  num_gts[b] is clamped to [0, max_gts]; max_gts == 0
+ * is legal.  No workspace. */
+int32_t frh_ga_targets(int32_t batch, int32_t num_levels, const int32_t* grid_hw, const float* strides,
+                       const float* gts, int64_t gt_seg_stride, const int32_t* num_gts,
+                       const int32_t* gt_levels, int32_t max_gts, const int32_t* img_hw, float center_ratio,
+                       float ignore_ratio, float shape_center_ratio, int64_t* loc, int64_t* shape_mask,
+                       float* shape_box, void* stream);
+
 /* ---------------------------------------------------------------- backbone epilogue
  * Frozen BatchNorm (+ residual) (+ ReLU) of the reference ResNet's bottlenecks
  * (lib/backbones.py:69-76 keeps every BN in eval mode; torchvision Bottleneck.forward):
@@ -642,6 +668,51 @@ size_t frh_roi_conv3x3_workspace(int32_t cin, int32_t cout);
 int32_t frh_roi_conv3x3_bn_act(const float* x, const float* w, float* y, const float* gamma, const float* beta,
                                const float* mean, const float* var, float eps, int64_t r, int32_t cin,
                                int32_t cout, int32_t relu, float* workspace, void* stream);
+
+/* The Guided Anchoring adaption layer (lib/heads/guided_head.py:92-96 offset_layer / adapt_layer,
+ * :404-405 GuidedAnchor.forward: DeformConv(cin, cout, 3, padding=1, deformable_groups=dg) on the
+ * offsets of a 1x1 conv of the shape map, then ReLU): a deformable (DCNv1, as mmdet v1's
+ * mmdet.ops.dcn.DeformConv and torchvision's deform_conv2d define it) 3x3 / stride-1 / padding-1 /
+ * dilation-1 convolution without bias, y = act(sum_{c, k} w[co, c, k] * sample(x, c, k)), as an
+ * implicit GEMM on the f32 MFMA fed by a bilinear gather (two launches: the weight repack into
+ * the workspace, which is redone on every call, then the convolution).
+ * Input channel c is in deformable group g = c / (cin / dg).  Tap k = 3 (ky + 1) + (kx + 1),
+ * ky, kx in {-1, 0, 1}, of group g at output (y, x) samples at (py, px) = (y + ky + dy,
+ * x + kx + dx) with dy = offset channel g * 18 + 2 k and dx = channel g * 18 + 2 k + 1 at (y, x).
+ * The sample is 0 unless -1 < py < h and -1 < px < wd; the test is made in float before any
+ * conversion to an integer, so a non-finite or huge offset gives 0 and forms no address.
+ * Otherwise it is bilinear from the four neighbours, ((hy hx) v00 + (hy lx) v01) + (ly hx) v10 +
+ * (ly lx) v11 with ly = py - floor(py), hy = 1 - ly, neighbours outside the map contributing 0.
+ * x: f32 [n, h, wd, cin] with channel stride 1 and element strides sn / sy / sx (image, row,
+ * column; non-negative multiples of 4, sx >= cin, so P5[:, :, ::2, ::2] runs without a copy);
+ * w: the weight [cout, cin, 3, 3], contiguous; y: contiguous NHWC [n, h, wd, cout]; workspace:
+ * frh_deform_conv3x3_workspace(cin, cout) bytes.
+ * offset_w == NULL (explicit): offset is f32 [n, 18 dg, h, wd] with the element strides
+ * offset_strides[0..3] (image, channel, row, column; any values).
+ * offset_w != NULL (guided): offset is the 2-channel shape map [n, 2, h, wd] with those
+ * strides and offset_w the offset layer's weight [18 dg, 2], contiguous; offset channel c is
+ * formed in registers as (offset_w[c][0] * s0) + (offset_w[c][1] * s1), in this f32 order -- the
+ * bits of the 1x1 convolution without bias -- and the 18 dg-channel map is never written.  The
+ * result is bit for bit that of the explicit mode on that map.
+ * cin % 16 == 0, (cin / dg) % 4 == 0, cout % 64 == 0, x / y / w / workspace / offset_w 16-byte
+ * aligned, y overlapping none of the other tensors (anything else: FRH_EINVAL); a level of 2^31
+ * positions or more: FRH_EUNSUPPORTED; n == 0 launches nothing.  The sums run in one fixed
+ * order (tap-major, then channel) with no atomics: the same inputs give the same bits on every
+ * launch, and an image's bits depend neither on n nor on its index.
+ * _levels: num_levels (1..8) inputs xs[i] [n, level_hw[2i], level_hw[2i + 1], cin] with strides
+ * level_strides[3i..] = (sn, sy, sx), offsets[i] with offset_strides[4i..] and outputs ys[i],
+ * sharing w and offset_w, in one repack launch and one convolution launch.  Each level's bits
+ * are those of its own frh_deform_conv3x3_act call. */
+size_t frh_deform_conv3x3_workspace(int32_t cin, int32_t cout);
+int32_t frh_deform_conv3x3_act(const float* x, const float* offset, const float* offset_w, const float* w,
+                               float* y, float* workspace, int64_t n, int32_t cin, int32_t cout, int32_t dg,
+                               int32_t h, int32_t wd, int64_t sn, int64_t sy, int64_t sx,
+                               const int64_t* offset_strides, int32_t relu, void* stream);
+int32_t frh_deform_conv3x3_act_levels(int32_t num_levels, const void* const* xs, const void* const* offsets,
+                                      const float* offset_w, const float* w, void* const* ys, float* workspace,
+                                      int64_t n, int32_t cin, int32_t cout, int32_t dg, const int32_t* level_hw,
+                                      const int64_t* level_strides, const int64_t* offset_strides, int32_t relu,
+                                      void* stream);
 
 /* FPN top-down merge into channels-last levels (lib/necks.py:72-84):
  * out[b, y, x, c] = (lat[b, c, y, x] + bias[c]) + up[b, iy, ix, c] with torch's nearest rule

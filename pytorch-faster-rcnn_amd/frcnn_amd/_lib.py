@@ -117,6 +117,13 @@ SIGNATURES = {
     'frh_roi_conv3x3_workspace': (c_size, [c_i32, c_i32]),
     'frh_roi_conv3x3_bn_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_i32, c_vp,
                                        c_vp]),
+    'frh_deform_conv3x3_workspace': (c_size, [c_i32, c_i32]),
+    'frh_deform_conv3x3_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                       c_i64, c_i64, c_i64, P(c_i64), c_i32, c_vp]),
+    'frh_deform_conv3x3_act_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), c_vp, c_vp, P(c_vp), c_vp, c_i64, c_i32, c_i32,
+                                              c_i32, P(c_i32), P(c_i64), P(c_i64), c_i32, c_vp]),
+    'frh_ga_targets': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32,
+                               c_f32, c_vp, c_vp, c_vp, c_vp]),
     'frh_bn_act_maxpool': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'frh_loss_workspace': (c_size, []),
     'frh_fpn_merge_nhwc': (c_i32, [c_vp, P(c_i64), c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),

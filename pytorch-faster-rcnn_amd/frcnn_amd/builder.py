@@ -11,15 +11,15 @@ from .backbones import ResNet, ResLayerC5
 from .necks import FPN, BFP
 from .region import MaxIoUAssigner, RandomSampler, IoUBalancedNegSampler, BasicRoIExtractor
 from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, CrossEntropyLoss, GIoULoss, IoULoss, QualityFocalLoss,
-                     DistributionFocalLoss)
-from .heads import RPNHead, RCNNHead, DoubleHead, RetinaHead, FCOSHead
+                     DistributionFocalLoss, BoundedIoULoss)
+from .heads import RPNHead, RCNNHead, DoubleHead, RetinaHead, FCOSHead, GARPNHead
 from .detectors import CascadeRCNN, RetinaNet, FCOS
 from .ops import RoIAlign, RoIPool
 
 _MODULE_LIST = [RetinaNet, CascadeRCNN, FCOS, ResNet, ResLayerC5, FPN, RetinaHead, RPNHead, RCNNHead, FCOSHead,
                 CrossEntropyLoss, SmoothL1Loss, FocalLoss, GIoULoss, IoULoss, QualityFocalLoss, DistributionFocalLoss,
                 BasicRoIExtractor, RoIAlign, RoIPool, SGD, MaxIoUAssigner, RandomSampler, BFP, IoUBalancedNegSampler,
-                BalancedL1Loss, DoubleHead]
+                BalancedL1Loss, DoubleHead, GARPNHead, BoundedIoULoss]
 
 MODULES = {cls.__name__: cls for cls in _MODULE_LIST}
 

@@ -76,6 +76,14 @@ class CascadeRCNN(nn.Module):
 
     def _forward_train(self, img_data, gt_bboxes, gt_labels, img_metas):
         losses = {}
+        if utils.class_name(self.rpn_head) == 'GARPNHead':
+            # cascade_rcnn.py:98-104: five outputs per level, a loss dict of four terms, the gt
+            # labels as they are; its proposals are plain per-image lists (no flat buffer)
+            feats = self.extract_feat(img_data)
+            res = tuple(self.rpn_head(feats))
+            losses.update(self.rpn_head.loss(*(res + (gt_bboxes, gt_labels, img_metas, self.train_cfg.rpn))))
+            props = self.rpn_head.predict_bboxes_from_output(*(res + (img_metas, self.train_cfg.rpn_proposal)))[0]
+            return self._forward_train_stages(losses, feats, props, gt_bboxes, gt_labels, img_metas, sync_free=False)
         if self.graphed_trunk is not None and self.graphed_trunk.matches(img_data):
             feats, rpn_cls, rpn_reg = self.graphed_trunk(img_data)
         else:
@@ -89,7 +97,12 @@ class CascadeRCNN(nn.Module):
         l_cls, l_reg = self.rpn_head.loss(rpn_cls, rpn_reg, gt_bboxes, rpn_gt_labels, img_metas, cfg.rpn)
         losses['rpn_cls_loss'] = l_cls
         losses['rpn_reg_loss'] = l_reg
-        if self._sync_free_rcnn(feats):
+        return self._forward_train_stages(losses, feats, props, gt_bboxes, gt_labels, img_metas,
+                                          sync_free=self._sync_free_rcnn(feats))
+
+    def _forward_train_stages(self, losses, feats, props, gt_bboxes, gt_labels, img_metas, sync_free):
+        cfg = self.train_cfg
+        if sync_free:
             # one stage, device sampler: padded targets, all rows through RoIAlign and the head,
             # the loss divides by the device count -- no host synchronisation in the RCNN stage
             head, extractor, scfg = self.rcnn_head[0], self.roi_extractors[0], cfg.rcnn[0]

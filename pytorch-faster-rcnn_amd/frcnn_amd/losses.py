@@ -171,6 +171,24 @@ class CrossEntropyLoss(nn.Module):
         return F.cross_entropy(pred, label, reduction='none').sum() * self.loss_weight
 
 
+class BoundedIoULoss(nn.Module):
+    """losses.py:182-193: smooth-L1 (beta) of 1 - min(x / y, y / x) on x + 1e-6, y + 1e-6 against
+    zero, summed; the Guided Anchoring shape loss on (dw, dh).  loss_weight is accepted and, as in
+    the reference, not applied.  Torch ops (a few hundred sampled positives)."""
+
+    def __init__(self, beta=0.2, loss_weight=1.0):
+        super().__init__()
+        self.beta, self.loss_weight = beta, loss_weight
+
+    def forward(self, x, y):
+        if x.shape != y.shape:
+            raise AssertionError('BoundedIoULoss: x and y shapes differ')
+        x = x + 1e-6
+        y = y + 1e-6
+        loss = 1 - torch.min(x / y, y / x)
+        return smooth_l1_loss_v2(loss, loss.new_zeros(loss.size()), self.beta)
+
+
 def fused_kinds(loss_cls, loss_bbox):
     """True when head_losses can run this pair of loss modules as one launch."""
     return isinstance(loss_bbox, SmoothL1Loss) and isinstance(loss_cls, (FocalLoss, CrossEntropyLoss))

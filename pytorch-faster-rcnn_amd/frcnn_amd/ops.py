@@ -1532,6 +1532,154 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
         outs[i] = y
     return outs
 
+
+# ---------------------------------------------------------------- deformable 3x3 conv (GA-RPN)
+def deform_conv3x3_torch(x, offset, weight, dg, relu=False):
+    """The deformable 3x3 / stride-1 / padding-1 convolution of include/frcnn_amd.h
+    (frh_deform_conv3x3_act, DCNv1) restated as a gather and a matmul in torch ops, in x's dtype
+    and on x's device: the path autograd differentiates (training), and in f64 the numerics
+    reference of the tests.  x [n, cin, h, w], offset [n, 18 dg, h, w], weight [cout, cin, 3, 3]."""
+    n, cin, H, W = x.shape
+    cout, cpg = weight.shape[0], cin // dg
+    if weight.shape[1:] != (cin, 3, 3) or cin % dg or offset.shape != (n, 18 * dg, H, W):
+        raise AssertionError('deform_conv3x3: weight [cout, cin, 3, 3] and offset [n, 18 dg, h, w] expected')
+    dt, dev = x.dtype, x.device
+    off = offset.to(dt).reshape(n, dg, 9, 2, H, W)
+    ky = torch.arange(9, device=dev).div(3, rounding_mode='floor').sub(1).to(dt).view(1, 1, 9, 1, 1)
+    kx = torch.arange(9, device=dev).remainder(3).sub(1).to(dt).view(1, 1, 9, 1, 1)
+    py = (torch.arange(H, dtype=dt, device=dev).view(1, 1, 1, H, 1) + ky) + off[:, :, :, 0]
+    px = (torch.arange(W, dtype=dt, device=dev).view(1, 1, 1, 1, W) + kx) + off[:, :, :, 1]
+    ok = (py > -1) & (py < H) & (px > -1) & (px < W)  # False for NaN
+    py, px = torch.where(ok, py, torch.zeros_like(py)), torch.where(ok, px, torch.zeros_like(px))
+    fy, fx = py.floor(), px.floor()
+    ly, lx = py - fy, px - fx
+    hy, hx = 1 - ly, 1 - lx
+    y0, x0 = fy.long(), fx.long()
+    xg = x.reshape(n, dg, cpg, H * W)
+
+    def corner(yy, xx, wgt):
+        valid = ok & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+        idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).view(n, dg, 1, 9 * H * W).expand(-1, -1, cpg, -1)
+        v = xg.gather(3, idx).view(n, dg, cpg, 9, H, W)
+        return v * (wgt * valid.to(dt)).unsqueeze(2)
+
+    s = ((corner(y0, x0, hy * hx) + corner(y0, x0 + 1, hy * lx)) + corner(y0 + 1, x0, ly * hx)) \
+        + corner(y0 + 1, x0 + 1, ly * lx)
+    y = torch.matmul(weight.to(dt).reshape(cout, cin * 9), s.reshape(n, cin * 9, H * W)).view(n, cout, H, W)
+    return torch.relu(y) if relu else y
+
+
+def _dc_x_ok(x, cin):
+    sn, sc, sy, sx = x.stride()
+    return (_f32_hip_4d(x) and x.shape[1] == cin and x.numel() > 0 and sc == 1 and sx >= cin and sy >= 0 and sn >= 0
+            and (sn | sy | sx) % 4 == 0)
+
+
+def deform_conv3x3_fused_ok(x, offset, weight, dg, offset_weight=None):
+    """Whether deform_conv3x3 / deform_conv3x3_levels take the HIP entry for these arguments
+    (offset_weight given: `offset` is the 2-channel shape map of the guided mode)."""
+    if not (torch.is_tensor(weight) and weight.dim() == 4 and weight.is_cuda and weight.dtype == torch.float32
+            and weight.is_contiguous() and weight.shape[2:] == (3, 3)):
+        return False
+    cout, cin = weight.shape[:2]
+    if cin % 16 or cout % 64 or dg < 1 or cin % dg or (cin // dg) % 4:
+        return False
+    och = 2 if offset_weight is not None else 18 * dg
+    if not (_dc_x_ok(x, cin) and _f32_hip_4d(offset)
+            and offset.shape == (x.shape[0], och, x.shape[2], x.shape[3])):
+        return False
+    if offset_weight is not None and not (offset_weight.is_cuda and offset_weight.dtype == torch.float32
+                                          and offset_weight.is_contiguous() and offset_weight.numel() == 36 * dg):
+        return False
+    return _aligned16(x, weight, offset_weight) and not _needs_grad(x, offset, weight, offset_weight)
+
+
+def _dc_ws(cin, cout, dev):
+    """The repacked-weight workspace of one call (every call rewrites it)."""
+    return torch.empty(9 * cin * cout, dtype=torch.float32, device=dev)
+
+
+def _as_channels_last(x):
+    return x if x.stride(1) == 1 else x.contiguous(memory_format=torch.channels_last)
+
+
+def deform_conv3x3(x, offset, weight, dg, relu=False, offset_weight=None):
+    """act(DeformConv(x, offset)) for a 3x3 / stride-1 / padding-1 deformable convolution without
+    bias: the HIP entry (frh_deform_conv3x3_act; the result is channels-last) when the tensors
+    are f32 on the HIP device, meet its shape conditions and nothing needs a gradient;
+    otherwise deform_conv3x3_torch, which autograd differentiates (training).  With
+    offset_weight [18 dg, 2(, 1, 1)] (guided mode) `offset` is the 2-channel shape map and the
+    offsets are the bias-free 1x1 convolution of it, formed inside the kernel."""
+    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
+    if x.is_cuda and x.dim() == 4:
+        x = _as_channels_last(x)
+    if not deform_conv3x3_fused_ok(x, offset, weight, dg, ow):
+        if ow is not None:
+            offset = nn.functional.conv2d(offset, ow.view(18 * dg, 2, 1, 1))
+        return deform_conv3x3_torch(x, offset, weight, dg, relu)
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    sn, _, sy, sx = x.stride()
+    y = _nhwc_empty((n, cout, h, w), x.device)
+    call('frh_deform_conv3x3_act', ptr(x), ptr(offset), ptr(ow), ptr(weight), ptr(y), ptr(_dc_ws(cin, cout, x.device)),
+         n, cin, cout, int(dg), h, w, sn, sy, sx, i64_array(offset.stride()), int(bool(relu)), stream_of(x))
+    return y
+
+
+def deform_conv3x3_levels(xs, offsets, weight, dg, relu=False, offset_weight=None):
+    """deform_conv3x3 with one shared weight on every level of a pyramid (at most 8): one repack
+    launch and one convolution launch (frh_deform_conv3x3_act_levels) when every level can take
+    the HIP entry; the per-level calls otherwise.  Same bits as the per-level calls."""
+    xs, offsets = list(xs), list(offsets)
+    if len(xs) != len(offsets):
+        raise AssertionError('deform_conv3x3_levels: one offset (or shape) map per level')
+    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
+    xs = [_as_channels_last(x) if x.is_cuda and x.dim() == 4 else x for x in xs]
+    if not (1 <= len(xs) <= 8 and all(deform_conv3x3_fused_ok(x, o, weight, dg, ow) for x, o in zip(xs, offsets))
+            and len({(x.shape[0], x.device) for x in xs}) == 1):
+        return [deform_conv3x3(x, o, weight, dg, relu, offset_weight) for x, o in zip(xs, offsets)]
+    n, dev = xs[0].shape[0], xs[0].device
+    cout, cin = weight.shape[:2]
+    ys = [_nhwc_empty((n, cout, x.shape[2], x.shape[3]), dev) for x in xs]
+    call('frh_deform_conv3x3_act_levels', len(xs), ptr_array(xs), ptr_array(offsets), ptr(ow), ptr(weight),
+         ptr_array(ys), ptr(_dc_ws(cin, cout, dev)), n, cin, cout, int(dg), *_level_geometry(xs),
+         i64_array([v for o in offsets for v in o.stride()]), int(bool(relu)), stream_of(xs[0]))
+    return ys
+
+
+def ga_targets(grid_sizes, strides, gt_list, level_list, img_shapes, center_ratio, ignore_ratio, shape_center_ratio):
+    """Batched GuidedAnchor.loc_target and the painting of shape_target_single_image_v2
+    (guided_head.py:342-397, :195-231) in one launch (csrc/ga.hip).  grid_sizes / strides: per
+    level; gt_list: per image [4, G_i] on the HIP device, coordinates >= 0; level_list: per image
+    [G_i] integer levels (region.map_gt2level); img_shapes: per image (h, w).  Returns loc i64
+    [B, N] (1 / 0 / -1), shape_mask i64 [B, N] and shape_box f32 [B, N, 4] over the
+    level-concatenated cells."""
+    _need_cuda(*gt_list)
+    if not gt_list:
+        raise AssertionError('ga_targets: at least one image expected')
+    dev = gt_list[0].device
+    B, L = len(gt_list), len(grid_sizes)
+    if len(strides) != L or len(level_list) != B or len(img_shapes) != B:
+        raise AssertionError('ga_targets: a stride per level, a level list and a shape per image')
+    N = sum(int(h) * int(w) for h, w in grid_sizes)
+    gts, gcnt, gmax = pack_boxes([g.float() for g in gt_list], dev)
+    lvls = torch.zeros(B, max(gmax, 1), dtype=torch.int32, device=dev)
+    for b, lv in enumerate(level_list):
+        if lv.numel() != gt_list[b].shape[1]:
+            raise AssertionError('ga_targets: one level per gt')
+        if lv.numel():
+            lvls[b, :lv.numel()] = lv.to(torch.int32)
+    img_hw = device_ints([int(v) for s in img_shapes for v in s[:2]], dev)
+    loc = torch.empty(B, N, dtype=torch.int64, device=dev)
+    mask = torch.empty(B, N, dtype=torch.int64, device=dev)
+    box = torch.empty(B, N, 4, dtype=torch.float32, device=dev)
+    hw = i32_array([int(v) for g in grid_sizes for v in g])
+    call('frh_ga_targets', B, L, hw, f32_array(strides), ptr(gts), gts.stride(0), ptr(gcnt), ptr(lvls), gmax,
+         ptr(img_hw), float(center_ratio), float(ignore_ratio), float(shape_center_ratio), ptr(loc), ptr(mask),
+         ptr(box), stream_of(loc))
+    return loc, mask, box
+
+
 def bn_act_maxpool(x, bn, pool):
     """pool(relu(bn(x))) for the ResNet stem (eval-mode BN, MaxPool2d(3, 2, 1)) in one HIP pass
     (frh_bn_act_maxpool) when nothing needs a gradient through it (the reference freezes the

@@ -14,7 +14,8 @@ def inside_grid_mask(num_anchors, img_size, grid_size, stride, device=None):
     r = 1.0 / stride
     ih, iw = min(gh, int(img_size[0] * r) + 1), min(gw, int(img_size[1] * r) + 1)
     dev = device if device is not None and torch.device(device).type == 'cuda' else torch.device('cuda')
-    dummy = torch.empty(4, 1, dtype=torch.float32, device=dev)
+    # ops.inside_mask sizes its mask by the anchors' columns (with border -1 it does not read them)
+    dummy = torch.empty(4, int(num_anchors) * gh * gw, dtype=torch.float32, device=dev)
     m = ops.inside_mask(dummy, [(gh, gw)], [(ih, iw)], num_anchors, 0, 0, -1)
     return m.float()
 
@@ -29,6 +30,16 @@ def inside_anchor_mask(anchors, img_size, allowed_border=0):
         a = a.contiguous()
     m = ops.inside_mask(a, [(1, n)], [(1, n)], 1, img_size[0], img_size[1], allowed_border)
     return m.bool()
+
+
+def map_gt2level(scale, strides, gt_bbox):
+    """region.py:31-40 with its index slip repaired (the reference reads gt[2] - gt[1] for the
+    width; DESIGN section 0, GA-RPN deviation 3): the level of each gt [4, n] is
+    floor(log2(sqrt(w h) / (scale * strides[0]))) with w = x2 - x1, h = y2 - y1 (no +1), clamped
+    to the levels there are."""
+    gt_sides = torch.sqrt((gt_bbox[2] - gt_bbox[0]) * (gt_bbox[3] - gt_bbox[1]))
+    gt_sides = gt_sides / (scale * strides[0])
+    return torch.log2(gt_sides).floor().long().clamp(0, len(strides) - 1)
 
 
 class MaxIoUAssigner(object):
