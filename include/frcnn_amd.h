@@ -650,6 +650,27 @@ int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, c
                                     const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
                                     void* stream);
 
+/* A bottleneck's 3x3 / stride-1 / padding-1 convolution (torchvision Bottleneck.forward: conv2,
+ * followed by its frozen BN and ReLU) as Winograd F(2x2, 3x3) on the f32 MFMA with the
+ * frh_bn_act epilogue on the accumulators: y[n, co] = act(conv3x3(x[n], w[co]) * s[co] + b[co]),
+ * zero padding, no dilation, no groups, no bias, s and b as in frh_bn_act.  Two launches: the
+ * weight transform into the workspace, which is redone on every call (nothing is cached), then
+ * the convolution.  x [n, cin, h, wd], y [n, cout, h, wd] contiguous NCHW f32; w the Conv2d
+ * weight [cout, cin, 3, 3], contiguous; workspace: frh_conv3x3_nchw_workspace(cin, cout) bytes.
+ * Any h; wd % 2 == 0 (rows are read and written as aligned float pairs), cin % 4 == 0,
+ * cout % 16 == 0, cin * h * wd and cout * h * wd below 2^31, every pointer 16-byte aligned,
+ * neither y nor the workspace sharing a byte with x or w, nor with each other (anything else:
+ * FRH_EINVAL and no launch); n == 0 or an empty plane launches nothing.  gamma / beta may be
+ * NULL (1 / 0); mean == var == NULL: no BN (the raw convolution, plus ReLU when relu).  The sum
+ * over cin runs in ascending order with no atomics and no split: the same inputs give the same
+ * bits on every launch, an image's bits do not depend on n, and with a BN the result is bit
+ * for bit frh_bn_act applied to the raw output of the same entry. */
+size_t frh_conv3x3_nchw_workspace(int32_t cin, int32_t cout);
+int32_t frh_conv3x3_nchw_bn_act(const float* x, const float* w, const float* gamma, const float* beta,
+                                const float* mean, const float* var, float eps, float* y, float* workspace,
+                                int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd, int32_t relu,
+                                void* stream);
+
 /* The Double-Head regression branch's conv over RoI tiles (lib/heads/double_head.py:63-76,
  * 119-122: Conv2d(cin, cout, 3, padding=1, bias=False), BatchNorm2d in eval mode, ReLU):
  * y[i, co, p] = act((sum_ci sum_tap w[co, ci, tap] * x[i, ci, p + tap]) * s[co] + b[co]) over

@@ -16,7 +16,8 @@ import logging
 import torch
 from torch import nn
 
-from .ops import bn_act_maxpool, conv1x1_bn_act, conv1x1_s2_bn_act
+from .ops import (bn_act_maxpool, conv1x1_bn_act, conv1x1_pre_fused_ok, conv1x1_s2_bn_act, conv3x3_nchw_bn_act,
+                  conv3x3_nchw_fused_ok)
 
 # blocks per stage for each depth
 _STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -48,13 +49,25 @@ class Bottleneck(nn.Module):
         # gradient (ops.conv1x1_bn_act, ops.conv1x1_s2_bn_act for the stride-2 projections; every
         # training path falls through to conv + ops.bn_act).  The 3x3 conv's BN + ReLU is applied
         # on conv3's input side (pre_bn), or by one HIP epilogue pass (ops.bn_act) where it cannot.
+        # A stride-1 3x3 conv runs as the fused NCHW Winograd entry where its class is dispatched
+        # (ops.conv3x3_nchw_bn_act): raw where conv3 takes bn2 on its input side, with bn2 + ReLU
+        # in its own epilogue where conv3 cannot (no separate pass either way).
         y = conv1x1_bn_act(self.conv1, self.bn1, x)
-        y = self.conv2(y)
+        fused2 = conv3x3_nchw_fused_ok(self.conv2, y, self.bn2)
+        if not fused2:
+            y = self.conv2(y)  # before the projection, as ever: the order of the autograd graph
         skip = x
         if self.do_downsample:
             proj = conv1x1_s2_bn_act if self.downsample[0].stride == (2, 2) else conv1x1_bn_act
             skip = proj(self.downsample[0], self.downsample[1], x, relu=False)
-        return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip, pre_bn=self.bn2)
+        if not fused2:
+            return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip, pre_bn=self.bn2)
+        # y stands in for conv2's output in conv3's predicate: same shape, layout and allocator
+        if conv1x1_pre_fused_ok(self.conv3, self.bn3, y, self.bn2, skip):
+            y = conv3x3_nchw_bn_act(self.conv2, y)
+            return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip, pre_bn=self.bn2)
+        y = conv3x3_nchw_bn_act(self.conv2, y, self.bn2, relu=True)
+        return conv1x1_bn_act(self.conv3, self.bn3, y, skip=skip)
 
 
 class ResNet(nn.Module):

@@ -1533,6 +1533,51 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
     return outs
 
 
+# Channel classes (cin, cout) at which tools/bench_conv3x3_nchw.py measured frh_conv3x3_nchw_bn_act
+# (weight transform included) slower than MIOpen's NCHW 3x3 conv, plus frh_bn_act where the
+# entry's epilogue replaces one (both times in DESIGN section 4): they keep the module.  A class
+# is dispatched only where the fused side's slowest repetition beat the module's fastest.
+_CONV3X3_NCHW_EXCLUDED = frozenset([(128, 128), (512, 512)])
+
+
+def conv3x3_nchw_fused_ok(conv, x, bn=None):
+    """Whether conv3x3_nchw_bn_act takes the fused HIP entry for these arguments.  Only with grad
+    mode off (the graphed trunk, inference): a training step runs the module even through a frozen
+    stage, so every training step computes exactly what it computed before this entry existed."""
+    if torch.is_grad_enabled():
+        return False
+    if not (_f32_hip_4d(x) and x.is_contiguous() and _conv_is(conv, 3, 1, 1) and conv.bias is None
+            and conv.weight.is_contiguous() and (bn is None or _frozen_bn(bn))):
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    n, c, h, w = x.shape
+    if c != cin or cin % 4 or cout % 16 or w % 2 or x.numel() == 0 or h * w >= 1 << 27 \
+            or max(cin, cout) * h * w >= 1 << 31 or cin * cout >= 1 << 24 or (cin, cout) in _CONV3X3_NCHW_EXCLUDED:
+        return False
+    return _aligned16(x, conv.weight) and not _needs_grad(x, conv.weight, *((bn.weight, bn.bias) if bn is not None else ()))
+
+
+def conv3x3_nchw_bn_act(conv, x, bn=None, relu=False):
+    """act(bn(conv(x))) for a bottleneck's 3x3 / stride-1 / padding-1 conv on a contiguous NCHW f32
+    HIP input (bn None: the raw convolution) in one fused launch pair (frh_conv3x3_nchw_bn_act:
+    Winograd F(2x2, 3x3) on the f32 MFMA, the eval-mode BN / ReLU on the accumulators) with grad
+    mode off (the graphed trunk, inference); otherwise the module, followed by ops.bn_act where
+    there is a BN."""
+    if not conv3x3_nchw_fused_ok(conv, x, bn):
+        y = conv(x)
+        if bn is not None:
+            return bn_act(y, bn, relu=relu)
+        return torch.relu_(y) if relu else y
+    n, _, h, w = x.shape
+    cin, cout = conv.in_channels, conv.out_channels
+    y = torch.empty(n, cout, h, w, dtype=torch.float32, device=x.device)
+    ws = torch.empty(16 * cin * cout, dtype=torch.float32, device=x.device)
+    bn_args = _bn_args(bn) if bn is not None else (None, None, None, None, 0.0)
+    call('frh_conv3x3_nchw_bn_act', ptr(x), ptr(conv.weight), *bn_args, ptr(y), ptr(ws), n, cin, cout, h, w,
+         int(bool(relu)), stream_of(x))
+    return y
+
+
 # ---------------------------------------------------------------- deformable 3x3 conv (GA-RPN)
 def deform_conv3x3_torch(x, offset, weight, dg, relu=False):
     """The deformable 3x3 / stride-1 / padding-1 convolution of include/frcnn_amd.h

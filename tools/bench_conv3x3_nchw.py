@@ -1,0 +1,156 @@
+"""Per-class timing of frh_conv3x3_nchw_bn_act against the path it replaces.
+
+    python tools/bench_conv3x3_nchw.py [--out profiles/bottleneck_conv3x3/bench_conv3x3_nchw.json]
+
+For every stride-1 3x3 convolution class of the cfg2 trunk (ResNet-50 conv2, 2 images of
+608 x 1024; cin -> cout @ h x w with its count per step) it times
+  parent: F.conv2d (cudnn.benchmark warmed: MIOpen's search), followed by frh_bn_act (bn2 + ReLU)
+          where the entry's epilogue replaces that pass (stage 4, whose conv3 does not take bn2
+          on its input side);
+  fused:  frh_conv3x3_nchw_bn_act with the product's form choice, weight transform included;
+  formK:  every kernel form (0 .. 2) through the tools library (tools/build_tools.py),
+under no_grad, 20 calls back to back behind a torch.cuda._sleep between one event pair, three
+tensor sets in rotation, 7 repetitions with the sides alternating; median with [min, max].  A
+class is dispatched only when the fused side's slowest repetition beats the parent's fastest.
+The limit is the larger of Winograd FLOPs (16 multiply-adds per 2 x 2 outputs and channel pair)
+/ 157.3 TFLOP/s and algorithmic bytes (x, w read once, y written once) / 8 TB/s."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+sys.path.insert(0, HERE)
+
+N = 2
+# (cin = cout, h, w, launches per step, bn2 + ReLU in the epilogue, where)
+CLASSES = [
+    (64, 152, 256, 3, False, 'stage 1 conv2'),
+    (128, 76, 128, 3, False, 'stage 2 conv2'),
+    (256, 38, 64, 5, False, 'stage 3 conv2'),
+    (512, 19, 32, 2, True, 'stage 4 conv2'),
+]
+PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
+SETS, ITERS, REPS = 3, 20, 7
+FORMS = ['(2, 1)', '(1, 2)', '(1, 1)']
+
+
+def time_calls(fns, iters):
+    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(100000000)
+    e0.record()
+    for i in range(iters):
+        fns[i % len(fns)]()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'bottleneck_conv3x3', 'bench_conv3x3_nchw.json'))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_conv3x3_nchw needs a HIP device')
+    from frcnn_amd import _lib, ops
+    try:
+        import toolslib
+        tools = toolslib.load()
+    except (RuntimeError, OSError, AttributeError) as e:
+        print('tools library unavailable ({}): forms not timed'.format(e), file=sys.stderr)
+        tools = None
+    torch.backends.cudnn.benchmark = True
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    p = _lib.ptr
+    rows = []
+    with torch.no_grad():
+        for c, h, w, count, epi, where in CLASSES:
+            conv = torch.nn.Conv2d(c, c, 3, padding=1, bias=False).to(dev)
+            bn = torch.nn.BatchNorm2d(c).to(dev).eval()
+            bn.running_var.uniform_(0.5, 2.0)
+            bn.running_mean.uniform_(-1, 1)
+            bnp = (p(bn.weight), p(bn.bias), p(bn.running_mean), p(bn.running_var), float(bn.eps))
+            nobn = (None, None, None, None, 0.0)
+            xs = [torch.randn(N, c, h, w, device=dev) for _ in range(SETS)]
+            ys = [torch.empty(N, c, h, w, device=dev) for _ in range(SETS)]
+            yp = [torch.empty(N, c, h, w, device=dev) for _ in range(SETS)]
+            ws = torch.empty(16 * c * c, device=dev)
+            st = _lib.stream_of(xs[0])
+
+            def parent(i):
+                def run():
+                    raw = F.conv2d(xs[i], conv.weight, padding=1)
+                    if epi:
+                        _lib.call('frh_bn_act', p(raw), None, p(yp[i]), *bnp, N, c, h * w, 1, st)
+                    else:
+                        yp[i] = raw
+                return run
+
+            def entry(i, form=None):
+                a = (p(xs[i]), p(conv.weight), *(bnp if epi else nobn), p(ys[i]), p(ws), N, c, c, h, w, int(epi), st)
+                if form is None:
+                    return lambda: _lib.call('frh_conv3x3_nchw_bn_act', *a)
+
+                def run():
+                    if tools.frh_conv3x3_nchw_bn_act_form(form, *a) != 0:
+                        raise RuntimeError('frh_conv3x3_nchw_bn_act_form({}) failed'.format(form))
+                return run
+            sides = {'parent': [parent(i) for i in range(SETS)], 'fused': [entry(i) for i in range(SETS)]}
+            if tools is not None:
+                for f in range(len(FORMS)):
+                    sides['form{}'.format(f)] = [entry(i, f) for i in range(SETS)]
+            for fns in sides.values():
+                for f in fns:
+                    f()
+                    f()
+            torch.cuda.synchronize()
+            sides['parent'][0]()
+            sides['fused'][0]()
+            torch.cuda.synchronize()
+            maxdiff = float((yp[0] - ys[0]).abs().max() / yp[0].abs().max())
+            t = {k: [] for k in sides}
+            for _ in range(REPS):
+                for k, fns in sides.items():
+                    t[k].append(time_calls(fns, ITERS))
+            stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
+            flops = 2.0 * 16 * N * c * c * ((h + 1) // 2) * ((w + 1) // 2)
+            nbytes = 4.0 * (2 * N * c * h * w + 9 * c * c)
+            limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
+            row = {'where': where, 'cin': c, 'cout': c, 'hw': [h, w], 'launches_per_step': count,
+                   'bn_relu_epilogue': epi, 'excluded_in_ops': (c, c) in ops._CONV3X3_NCHW_EXCLUDED,
+                   'fused_wins': stat['fused'][2] < stat['parent'][1],
+                   'winograd_gflop': round(flops / 1e9, 3), 'algorithmic_MB': round(nbytes / 1e6, 2),
+                   'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
+                   'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / stat['fused'][0], 3),
+                   'parent_share_of_limit': round(limit_us / stat['parent'][0], 3),
+                   'max_rel_diff_vs_parent': maxdiff}
+            for k, (med, lo, hi) in stat.items():
+                row[k + '_us'] = round(med, 1)
+                row[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
+            rows.append(row)
+            print('{:14s} {:4d}->{:4d} @ {}x{} x{}  parent {:7.1f} [{:.1f}, {:.1f}]  fused {:7.1f} [{:.1f}, {:.1f}]  {}  '
+                  'limit {:.1f} us  wins {}  diff {:.1e}'.format(
+                      where, c, c, h, w, count, *stat['parent'], *stat['fused'],
+                      {k: round(v[0], 1) for k, v in stat.items() if k.startswith('form')}, limit_us,
+                      row['fused_wins'], maxdiff), flush=True)
+            del xs, ys, yp
+    res = {'device': torch.cuda.get_device_name(0), 'iters': ITERS, 'reps': REPS, 'batch': N, 'forms': FORMS,
+           'classes': rows,
+           'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
+           'per_step_fused_us': round(sum(r['fused_us'] * r['launches_per_step'] for r in rows), 1)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k != 'classes'}))
+
+
+if __name__ == '__main__':
+    main()

@@ -123,6 +123,14 @@ int32_t frh_conv1x1_bn_act_step(int32_t step, const float* x, const float* w, co
                                 const float* gamma, const float* beta, const float* mean, const float* var, float eps,
                                 int64_t n, int32_t cin, int32_t cout, int64_t hw, int32_t relu, void* stream);
 
+/* frh_conv3x3_nchw_bn_act with the kernel form given instead of chosen (conv3x3_nchw_kernels.h):
+ * 0 .. 2 = (tile rows, 16-channel blocks) per wave (2, 1), (1, 2), (1, 1); the form with two
+ * channel blocks needs cout % 32 == 0. */
+int32_t frh_conv3x3_nchw_bn_act_form(int32_t form, const float* x, const float* w, const float* gamma,
+                                     const float* beta, const float* mean, const float* var, float eps, float* y,
+                                     float* workspace, int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd,
+                                     int32_t relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

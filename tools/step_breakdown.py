@@ -27,6 +27,7 @@ CLASSES = [
     ('fused 1x1 conv + frozen-BN/residual/ReLU', ('conv1x1_bn_act',)),
     ('frozen-BN/residual/ReLU bn_act', ('bn_act',)),
     ('fused 3x3 Winograd conv + bias/ReLU (FPN outputs, RPN conv)', ('conv3x3_bias_act',)),
+    ('fused NCHW 3x3 Winograd conv + frozen-BN/ReLU (bottleneck conv2)', ('conv3x3_nchw',)),
     ('FPN merge (+ lateral bias), RPN conv bias + ReLU', ('fpn_merge', 'bias_act')),
     ('other frcnn_amd kernels', ('frh::',)),
     ('MIOpen convolutions', ('miopenSp3AsmConv', 'igemm_', 'naive_conv', 'kernel_grouped_conv', 'conv_', 'Im2d2Col')),
