@@ -23,8 +23,9 @@
 // Two LDS stages of each, one barrier per chunk.  While chunk t runs its MFMAs, U of chunk
 // t + 1 is in flight into the other U stage, the patch of chunk t + 2 is in flight into one of
 // two register sets, and the patch of chunk t + 1 (the other set, landed one step ago) is
-// transformed and written; all loads of a step are issued in its first 9 MFMAs and waited for
-// once, before its closing barrier.  The prologue is step -1 and past the last chunk the
+// transformed and written; the patch loads of a step are issued in its first 8 MFMAs, the DMA
+// in four pieces over the next 8, and all are waited for once, before its closing barrier.
+// The prologue is step -1 and past the last chunk the
 // prefetches repeat it, so every chunk count runs the same loop body and nothing is peeled.
 // LDS images: V [16][64 tiles][8 k] and U [16][64 cout][8 k]; lane half h owns
 // k = 4 h .. 4 h + 3 of the chunk (a fixed permutation of the k order), one ds_read_b128 per
@@ -84,7 +85,7 @@ struct Conv3x3Weights {
 // U = G g G^T of w [cout][3][3][cin] into [cin / 8][16][cout][8], rows in wg_slab_off order,
 // for weight blockIdx.y of the table.  One thread per (chunk, cout, k half): 9 float4 in,
 // 16 float4 out, a wave's stores contiguous.
-__global__ void __launch_bounds__(256) conv3x3_bias_act_weights_kernel(const Conv3x3Weights tab, int cin, int cout) {
+static __global__ void __launch_bounds__(256) conv3x3_bias_act_weights_kernel(const Conv3x3Weights tab, int cin, int cout) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (int64_t)(cin / kWgBK) * cout * 2) return;
   const float* w = tab.w[0];
@@ -153,7 +154,7 @@ __device__ __forceinline__ uint64_t wg_uniform64(const void* p) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-__global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const Conv3x3Args a) {
+static __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const Conv3x3Args a) {
   // 128 KB, one array: U stages 0, 1 (the LDS-DMA's targets), then V stages 0, 1
   __shared__ __attribute__((aligned(16))) float lds[4 * kWgImage];
 
@@ -227,38 +228,54 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
     FRH_WG_LX(S, 3, 0), FRH_WG_LX(S, 3, 1), FRH_WG_LX(S, 3, 2), FRH_WG_LX(S, 3, 3);              \
   } while (0)
 
-  // Chunk t of U into U stage ST by LDS-DMA: 8 instructions per wave, no registers.  In
-  // assembly, because the compiler makes every LDS read after a DMA it knows of wait for that
-  // DMA.  It does not count these, so FRH_WG_SYNC waits for them; the only orderings needed are
-  // held by operands: the token chains each DMA between the barriers before and after it, and
-  // `after` (a value made from the last patch register of the step) keeps it behind the
-  // compiler's counted waits for the patch loads, which it would otherwise tighten.  M0 is the
-  // LDS address of a run pair; it is the compiler's register, so it is put back.
-#define FRH_WG_DMA(ST, t, after)                                                                 \
+  // Position q (of the wave's four) of chunk t of U into U stage ST by LDS-DMA: one M0 value
+  // (the LDS address of the position's run pair) and two instructions, no registers; four such
+  // pieces move the wave's 8 KB.  In assembly, because the compiler makes every LDS read after
+  // a DMA it knows of wait for that DMA.  One statement for all eight instructions put 8 x
+  // 60-185 cycles of DMA issue into a single 64-cycle MFMA gap; a piece per gap is covered by
+  // its MFMA.  What orders a piece is held by operands alone:
+  //  - the token chains every piece behind the barrier that freed its stage (FRH_WG_SYNC of the
+  //    step before, after which no wave reads stage ST's U again until the next barrier) and
+  //    ahead of the step's own FRH_WG_SYNC, and the pieces among themselves;
+  //  - the compiler does not count these loads, so FRH_WG_SYNC's vmcnt(0) retires them, every
+  //    step and before the epilogue: no DMA is in flight when the workgroup ends and the next
+  //    one on the CU gets its LDS;
+  //  - `after` is a value of the column stage of B^T d B, which is made from the step's selects,
+  //    and these carry every s_waitcnt vmcnt(N) the compiler emits in a step (it counts the
+  //    patch loads of the step before, which FRH_WG_SYNC has retired already).  So every piece
+  //    sits behind the step's last counted wait, none of them is tightened by a load it does
+  //    not count, and the pieces land in the VALU-only gaps behind the 16 patch loads (emitted:
+  //    MFMA gaps 10, 12, 14, 16 of the step);
+  //  - M0 is the compiler's register, so each piece puts it back.
+  // The s_nop 4 covers a VALU-written SGPR (readfirstlane) read by the DMA, the s_nop 0 the
+  // M0 write ahead of it: the compiler's hazard pass does not look into the statement.
+#define FRH_WG_DMA_PIECE(ST, t, q, after)                                                        \
   do {                                                                                           \
-    const uint64_t g_ = wg_uniform64(ub + (int64_t)(t) * u_chunk);                               \
-    const uint32_t l_ = u_dst + (ST) * kWgImage * 4;                                             \
+    const uint64_t g_ = wg_uniform64(ub + (int64_t)(t) * u_chunk) + (q) * u_pos;                 \
+    const uint32_t l_ = u_dst + (ST) * kWgImage * 4 + (q) * kWgSlab * 4;                         \
     uint32_t m0_;                                                                                \
     asm("s_nop 4\n\t"                                                                            \
         "s_mov_b32 %0, m0\n\t"                                                                   \
         "s_mov_b32 m0, %3\n\ts_nop 0\n\t"                                                        \
-        "global_load_lds_dwordx4 %2, %7\n\tglobal_load_lds_dwordx4 %2, %7 offset:1024\n\t"       \
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\t"                                                        \
-        "global_load_lds_dwordx4 %2, %8\n\tglobal_load_lds_dwordx4 %2, %8 offset:1024\n\t"       \
-        "s_mov_b32 m0, %5\n\ts_nop 0\n\t"                                                        \
-        "global_load_lds_dwordx4 %2, %9\n\tglobal_load_lds_dwordx4 %2, %9 offset:1024\n\t"       \
-        "s_mov_b32 m0, %6\n\ts_nop 0\n\t"                                                        \
-        "global_load_lds_dwordx4 %2, %10\n\tglobal_load_lds_dwordx4 %2, %10 offset:1024\n\t"     \
+        "global_load_lds_dwordx4 %2, %4\n\tglobal_load_lds_dwordx4 %2, %4 offset:1024\n\t"       \
         "s_mov_b32 m0, %0"                                                                       \
         : "=&s"(m0_), "+v"(token)                                                                \
-        : "v"(u_lane), "s"(l_), "s"(l_ + kWgSlab * 4), "s"(l_ + 2 * kWgSlab * 4),                \
-          "s"(l_ + 3 * kWgSlab * 4), "s"(g_), "s"(g_ + u_pos), "s"(g_ + 2 * u_pos),              \
-          "s"(g_ + 3 * u_pos), "v"(after));                                                      \
+        : "v"(u_lane), "s"(l_), "s"(g_), "v"(after));                                            \
   } while (0)
 
-  // B^T d B of patch set S into V stage ST: columns first (e = B^T d), then rows, each V row
+  // B^T d B of patch set S into V stage ST: the selects and the columns (e = B^T d) as values
+  // of the enclosing block, which the DMA pieces are ordered behind, then the rows, each V row
   // written as soon as it is complete
 #define FRH_WG_Z(S, r, c) (xok[r][c] ? x##S##r##c : z2)
+#define FRH_WG_VCOLS(S)                                                                                    \
+  const wg_f32x2 d00 = FRH_WG_Z(S, 0, 0), d01 = FRH_WG_Z(S, 0, 1), d02 = FRH_WG_Z(S, 0, 2), d03 = FRH_WG_Z(S, 0, 3); \
+  const wg_f32x2 d10 = FRH_WG_Z(S, 1, 0), d11 = FRH_WG_Z(S, 1, 1), d12 = FRH_WG_Z(S, 1, 2), d13 = FRH_WG_Z(S, 1, 3); \
+  const wg_f32x2 d20 = FRH_WG_Z(S, 2, 0), d21 = FRH_WG_Z(S, 2, 1), d22 = FRH_WG_Z(S, 2, 2), d23 = FRH_WG_Z(S, 2, 3); \
+  const wg_f32x2 d30 = FRH_WG_Z(S, 3, 0), d31 = FRH_WG_Z(S, 3, 1), d32 = FRH_WG_Z(S, 3, 2), d33 = FRH_WG_Z(S, 3, 3); \
+  const wg_f32x2 e00 = d00 - d20, e01 = d01 - d21, e02 = d02 - d22, e03 = d03 - d23;                       \
+  const wg_f32x2 e10 = d10 + d20, e11 = d11 + d21, e12 = d12 + d22, e13 = d13 + d23;                       \
+  const wg_f32x2 e20 = d20 - d10, e21 = d21 - d11, e22 = d22 - d12, e23 = d23 - d13;                       \
+  const wg_f32x2 e30 = d10 - d30, e31 = d11 - d31, e32 = d12 - d32, e33 = d13 - d33
 #define FRH_WG_VROW(vp, e0, e1, e2, e3)                                   \
   do {                                                                    \
     *reinterpret_cast<wg_f32x2*>(vp) = (e0) - (e2);                       \
@@ -266,17 +283,13 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
     *reinterpret_cast<wg_f32x2*>((vp) + 2 * kWgSlab) = (e2) - (e1);       \
     *reinterpret_cast<wg_f32x2*>((vp) + 3 * kWgSlab) = (e1) - (e3);       \
   } while (0)
-#define FRH_WG_VSTORE(ST, S)                                                                               \
-  do {                                                                                                     \
-    const wg_f32x2 d00 = FRH_WG_Z(S, 0, 0), d01 = FRH_WG_Z(S, 0, 1), d02 = FRH_WG_Z(S, 0, 2), d03 = FRH_WG_Z(S, 0, 3); \
-    const wg_f32x2 d10 = FRH_WG_Z(S, 1, 0), d11 = FRH_WG_Z(S, 1, 1), d12 = FRH_WG_Z(S, 1, 2), d13 = FRH_WG_Z(S, 1, 3); \
-    const wg_f32x2 d20 = FRH_WG_Z(S, 2, 0), d21 = FRH_WG_Z(S, 2, 1), d22 = FRH_WG_Z(S, 2, 2), d23 = FRH_WG_Z(S, 2, 3); \
-    const wg_f32x2 d30 = FRH_WG_Z(S, 3, 0), d31 = FRH_WG_Z(S, 3, 1), d32 = FRH_WG_Z(S, 3, 2), d33 = FRH_WG_Z(S, 3, 3); \
-    float* vp = lds + (2 + (ST)) * kWgImage + v_off;                                                       \
-    FRH_WG_VROW(vp, d00 - d20, d01 - d21, d02 - d22, d03 - d23);                                           \
-    FRH_WG_VROW(vp + 4 * kWgSlab, d10 + d20, d11 + d21, d12 + d22, d13 + d23);                             \
-    FRH_WG_VROW(vp + 8 * kWgSlab, d20 - d10, d21 - d11, d22 - d12, d23 - d13);                             \
-    FRH_WG_VROW(vp + 12 * kWgSlab, d10 - d30, d11 - d31, d12 - d32, d13 - d33);                            \
+#define FRH_WG_VROWS(ST)                                                  \
+  do {                                                                    \
+    float* vp = lds + (2 + (ST)) * kWgImage + v_off;                      \
+    FRH_WG_VROW(vp, e00, e01, e02, e03);                                  \
+    FRH_WG_VROW(vp + 4 * kWgSlab, e10, e11, e12, e13);                    \
+    FRH_WG_VROW(vp + 8 * kWgSlab, e20, e21, e22, e23);                    \
+    FRH_WG_VROW(vp + 12 * kWgSlab, e30, e31, e32, e33);                   \
   } while (0)
 
 #define FRH_WG_MFMA(ST, p)                                                          \
@@ -305,8 +318,8 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   // so every step is this one body.  The stage is a literal so that the LDS reads and writes
   // of a step are provably disjoint, and the scheduling groups spread the staging work over
   // the MFMAs' issue gaps: per position the operand reads of the next one; in the first 8
-  // MFMAs four VALU (the selects that read the landed set) and two patch loads each, the DMA
-  // behind them; then two VALU per MFMA and V's LDS writes last.
+  // MFMAs four VALU (the selects that read the landed set) and two patch loads each; then the
+  // adds, four per MFMA as emitted, with one DMA piece in every second gap; V's LDS writes last.
 #define FRH_WG_GROUPS(N, VALU, MEM, K, ID)                                          \
   _Pragma("unroll") for (int p = 0; p < (N); ++p) {                                 \
     __builtin_amdgcn_sched_group_barrier(0x100, 2, ID);                             \
@@ -320,8 +333,12 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   do {                                                                              \
     _Pragma("unroll") for (int p = 0; p < 16; ++p) FRH_WG_MFMA(ST, p);              \
     FRH_WG_LOADX(ST, min((t) + 2, last));                                           \
-    FRH_WG_DMA(OT, min((t) + 1, last), FRH_WG_Z(OT, 3, 3).y);                       \
-    FRH_WG_VSTORE(OT, OT);                                                          \
+    FRH_WG_VCOLS(OT);                                                               \
+    FRH_WG_DMA_PIECE(OT, min((t) + 1, last), 0, e03.y);                             \
+    FRH_WG_DMA_PIECE(OT, min((t) + 1, last), 1, e13.y);                             \
+    FRH_WG_DMA_PIECE(OT, min((t) + 1, last), 2, e23.y);                             \
+    FRH_WG_DMA_PIECE(OT, min((t) + 1, last), 3, e33.y);                             \
+    FRH_WG_VROWS(OT);                                                               \
     __builtin_amdgcn_sched_group_barrier(0x100, 4, ST);                             \
     FRH_WG_GROUPS(2, 4, 0x020, 2, ST);                                              \
     FRH_WG_GROUPS(14, 2, 0x200, 1, ST);                                             \
@@ -336,10 +353,16 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
 
   const int last = a.cin / kWgBK - 1;
   uint32_t token = 0;
-  FRH_WG_DMA(0, 0, 0.0f);
+  FRH_WG_DMA_PIECE(0, 0, 0, 0.0f);
+  FRH_WG_DMA_PIECE(0, 0, 1, 0.0f);
+  FRH_WG_DMA_PIECE(0, 0, 2, 0.0f);
+  FRH_WG_DMA_PIECE(0, 0, 3, 0.0f);
   FRH_WG_LOADX(0, 0);
   FRH_WG_LOADX(1, min(1, last));
-  FRH_WG_VSTORE(0, 0);
+  {
+    FRH_WG_VCOLS(0);
+    FRH_WG_VROWS(0);
+  }
   FRH_WG_SYNC();
   for (int t = 0;; t += 2) {
     FRH_WG_STEP(0, 1, t);
@@ -349,10 +372,11 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   }
 #undef FRH_WG_LX
 #undef FRH_WG_LOADX
-#undef FRH_WG_DMA
+#undef FRH_WG_DMA_PIECE
 #undef FRH_WG_Z
+#undef FRH_WG_VCOLS
 #undef FRH_WG_VROW
-#undef FRH_WG_VSTORE
+#undef FRH_WG_VROWS
 #undef FRH_WG_MFMA
 #undef FRH_WG_SYNC
 #undef FRH_WG_GROUPS
@@ -363,6 +387,11 @@ __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const
   const int co = cb * kWgCout + wn * 32 + j;
   const bool has_bias = L.bias != nullptr;
   const float bias = has_bias ? L.bias[co] : 0.0f;
+  // The one wait for the bias, in the block that dominates every store.  Without it the
+  // compiler waits inside each conditional bias add, and past the join behind it the load
+  // counts as pending again: s_waitcnt vmcnt(0) before all 64 stores, which also retires the
+  // store before (stores count in vmcnt), so the stores went out one round trip at a time.
+  asm volatile("" : : "v"(bias));
   float* yb = L.y + (int64_t)img * H * W * a.cout + co;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -403,9 +432,12 @@ struct Conv3x3LevelDesc {
 
 // Runs `levels` levels in one launch of the main kernel, after one launch that transforms each
 // distinct weight (consecutive levels with the same w share one) into its slot of ws
-// ([16 * cin * cout] floats each; ws_floats is what the caller provides).
-inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3LevelDesc* d, float* ws,
-                              int64_t ws_floats, int64_t n, int32_t cin, int32_t cout, int32_t relu, void* stream) {
+// ([16 * cin * cout] floats each; ws_floats is what the caller provides).  main_launch(grid, a)
+// launches the main kernel: the product's below, a laboratory build of it in the tools library.
+template <class MainLaunch>
+inline int32_t conv3x3_launch_with(const char* what, int32_t levels, const Conv3x3LevelDesc* d, float* ws,
+                                   int64_t ws_floats, int64_t n, int32_t cin, int32_t cout, int32_t relu,
+                                   void* stream, MainLaunch&& main_launch) {
   FRH_REQUIRE(levels >= 1 && levels <= kWgMaxLevels, "1 to %d levels, got %d", kWgMaxLevels, levels);
   FRH_REQUIRE(n >= 0 && n < (1 << 20) && cin >= 1 && cout >= 1 && cout <= (1 << 20), "bad sizes");
   FRH_REQUIRE(cin % kWgBK == 0 && cout % kWgCout == 0, "cin %d must be a multiple of %d and cout %d of %d", cin,
@@ -451,9 +483,17 @@ inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3Lev
   const int64_t wt = (int64_t)(cin / kWgBK) * cout * 2;
   hipLaunchKernelGGL(conv3x3_bias_act_weights_kernel, dim3((unsigned)((wt + 255) / 256), (unsigned)slots), dim3(256),
                      0, as_stream(stream), tab, cin, cout);
-  hipLaunchKernelGGL(conv3x3_bias_act_wino_kernel, dim3((unsigned)(a.chunk * kWgXcds)), dim3(kWgThreads), 0,
-                     as_stream(stream), a);
+  main_launch(dim3((unsigned)(a.chunk * kWgXcds)), a);
   return check_launch(what);
+}
+
+inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3LevelDesc* d, float* ws,
+                              int64_t ws_floats, int64_t n, int32_t cin, int32_t cout, int32_t relu, void* stream) {
+  return conv3x3_launch_with(what, levels, d, ws, ws_floats, n, cin, cout, relu, stream,
+                             [&](dim3 grid, const Conv3x3Args& a) {
+                               hipLaunchKernelGGL(conv3x3_bias_act_wino_kernel, grid, dim3(kWgThreads), 0,
+                                                  as_stream(stream), a);
+                             });
 }
 
 }  // namespace frh

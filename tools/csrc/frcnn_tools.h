@@ -131,6 +131,21 @@ int32_t frh_conv3x3_nchw_bn_act_form(int32_t form, const float* x, const float* 
                                      float* workspace, int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd,
                                      int32_t relu, void* stream);
 
+/* frh_conv3x3_bias_act_levels with a laboratory build of the main kernel (conv3x3_wino_lab.hip):
+ * variant = 100 * DMA form (0 one statement, 1 four pieces behind the column stage, 2 four pieces
+ * behind the selects, 3 eight pieces) + positions multiplied before the step's barrier (16 = the
+ * barrier closes the step, 12 .. 15 = register tail) + 1000 if two positions' MFMAs alternate
+ * + 10000 * where the bias is loaded (0 behind the loop, 1 before it, 2 behind it with one wait);
+ * 20116 is the product's form, 16 the form before it; other sums fail.  stamps null, or 8 uint64 per logical
+ * workgroup: s_memtime, s_memrealtime at entry, before and after the main loop, after the
+ * epilogue (tools/clock_conv3x3.py). */
+int32_t frh_conv3x3_bias_act_levels_variant(int32_t variant, uint64_t* stamps, int32_t num_levels,
+                                            const void* const* xs, const void* const* weights,
+                                            const void* const* biases, void* const* ys, float* workspace,
+                                            size_t workspace_bytes, int64_t n, int32_t cin, int32_t cout,
+                                            const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
+                                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

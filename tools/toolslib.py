@@ -32,6 +32,7 @@ TOOL_SIGNATURES = {
     'frh_sample_random_stamped': (c_i32, _lib.SIGNATURES['frh_sample_random'][1][:-1] + [c_vp, c_vp]),
     'frh_conv1x1_bn_act_step': (c_i32, [c_i32] + _lib.SIGNATURES['frh_conv1x1_bn_act'][1]),
     'frh_conv3x3_nchw_bn_act_form': (c_i32, [c_i32] + _lib.SIGNATURES['frh_conv3x3_nchw_bn_act'][1]),
+    'frh_conv3x3_bias_act_levels_variant': (c_i32, [c_i32, c_vp] + _lib.SIGNATURES['frh_conv3x3_bias_act_levels'][1]),
 }
 _lib_t = None
 
