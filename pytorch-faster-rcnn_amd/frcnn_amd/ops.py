@@ -1536,8 +1536,9 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
 # Channel classes (cin, cout) at which tools/bench_conv3x3_nchw.py measured frh_conv3x3_nchw_bn_act
 # (weight transform included) slower than MIOpen's NCHW 3x3 conv, plus frh_bn_act where the
 # entry's epilogue replaces one (both times in DESIGN section 4): they keep the module.  A class
-# is dispatched only where the fused side's slowest repetition beat the module's fastest.
-_CONV3X3_NCHW_EXCLUDED = frozenset([(128, 128), (512, 512)])
+# is dispatched only where the fused side's slowest repetition beat the module's fastest.  Empty
+# since the cin-split forms: all four ResNet-50 classes are dispatched.
+_CONV3X3_NCHW_EXCLUDED = frozenset()
 
 
 def conv3x3_nchw_fused_ok(conv, x, bn=None):

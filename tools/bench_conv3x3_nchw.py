@@ -1,6 +1,7 @@
 """Per-class timing of frh_conv3x3_nchw_bn_act against the path it replaces.
 
     python tools/bench_conv3x3_nchw.py [--out profiles/bottleneck_conv3x3/bench_conv3x3_nchw.json]
+                                       [--parent-lib PATH/libfrcnn_amd.so] [--iters N --reps R --sides form1,form3]
 
 For every stride-1 3x3 convolution class of the cfg2 trunk (ResNet-50 conv2, 2 images of
 608 x 1024; cin -> cout @ h x w with its count per step) it times
@@ -8,13 +9,16 @@ For every stride-1 3x3 convolution class of the cfg2 trunk (ResNet-50 conv2, 2 i
           where the entry's epilogue replaces that pass (stage 4, whose conv3 does not take bn2
           on its input side);
   fused:  frh_conv3x3_nchw_bn_act with the product's form choice, weight transform included;
-  formK:  every kernel form (0 .. 2) through the tools library (tools/build_tools.py),
+  parent_lib: frh_conv3x3_nchw_bn_act of another build loaded beside this one (--parent-lib: the
+          parent commit's library, built from a clean export);
+  formK:  every kernel form (FORMS) through the tools library (tools/build_tools.py),
 under no_grad, 20 calls back to back behind a torch.cuda._sleep between one event pair, three
 tensor sets in rotation, 7 repetitions with the sides alternating; median with [min, max].  A
 class is dispatched only when the fused side's slowest repetition beats the parent's fastest.
 The limit is the larger of Winograd FLOPs (16 multiply-adds per 2 x 2 outputs and channel pair)
 / 157.3 TFLOP/s and algorithmic bytes (x, w read once, y written once) / 8 TB/s."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -38,7 +42,9 @@ CLASSES = [
 ]
 PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
 SETS, ITERS, REPS = 3, 20, 7
-FORMS = ['(2, 1)', '(1, 2)', '(1, 1)']
+# 0 .. 2: (NT, NC), one wave per work item; 3, 4: cin split S over a workgroup of S x TR waves (the
+# product's forms); 5 ..: the laboratory forms with U through LDS (tools/csrc/conv3x3_nchw_lab.hip)
+FORMS = ['(2, 1)', '(1, 2)', '(1, 1)', 'NC1 S4 TR1', 'NC1 S2 TR2', 'NC2 S1 TR4 lds', 'NC1 S2 TR2 lds', 'NC1 S1 TR4 lds']
 
 
 def time_calls(fns, iters):
@@ -56,6 +62,12 @@ def time_calls(fns, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'bottleneck_conv3x3', 'bench_conv3x3_nchw.json'))
+    ap.add_argument('--parent-lib', default=None, help="another build's libfrcnn_amd.so (the parent commit's, built "
+                    "from a clean export): its frh_conv3x3_nchw_bn_act is timed as the side parent_lib")
+    ap.add_argument('--iters', type=int, default=ITERS, help='calls per repetition')
+    ap.add_argument('--reps', type=int, default=REPS)
+    ap.add_argument('--sides', default='', help='comma-separated subset of parent,fused,form0.. (a counter pass '
+                    'times few launches of few sides; the parent and fused sides are needed for the comparison fields)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_conv3x3_nchw needs a HIP device')
@@ -66,6 +78,11 @@ def main():
     except (RuntimeError, OSError, AttributeError) as e:
         print('tools library unavailable ({}): forms not timed'.format(e), file=sys.stderr)
         tools = None
+    plib = None
+    if args.parent_lib:
+        plib = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        plib.frh_conv3x3_nchw_bn_act.restype, plib.frh_conv3x3_nchw_bn_act.argtypes = \
+            _lib.SIGNATURES['frh_conv3x3_nchw_bn_act']
     torch.backends.cudnn.benchmark = True
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
@@ -98,15 +115,24 @@ def main():
                 a = (p(xs[i]), p(conv.weight), *(bnp if epi else nobn), p(ys[i]), p(ws), N, c, c, h, w, int(epi), st)
                 if form is None:
                     return lambda: _lib.call('frh_conv3x3_nchw_bn_act', *a)
+                if form == 'parent_lib':
+                    def run_parent():
+                        if plib.frh_conv3x3_nchw_bn_act(*a) != 0:
+                            raise RuntimeError('the parent library\'s frh_conv3x3_nchw_bn_act failed')
+                    return run_parent
 
                 def run():
                     if tools.frh_conv3x3_nchw_bn_act_form(form, *a) != 0:
                         raise RuntimeError('frh_conv3x3_nchw_bn_act_form({}) failed'.format(form))
                 return run
             sides = {'parent': [parent(i) for i in range(SETS)], 'fused': [entry(i) for i in range(SETS)]}
+            if plib is not None:
+                sides['parent_lib'] = [entry(i, 'parent_lib') for i in range(SETS)]
             if tools is not None:
                 for f in range(len(FORMS)):
                     sides['form{}'.format(f)] = [entry(i, f) for i in range(SETS)]
+            if args.sides:
+                sides = {k: v for k, v in sides.items() if k in ('parent', 'fused', 'parent_lib') or k in args.sides.split(',')}
             for fns in sides.values():
                 for f in fns:
                     f()
@@ -117,9 +143,9 @@ def main():
             torch.cuda.synchronize()
             maxdiff = float((yp[0] - ys[0]).abs().max() / yp[0].abs().max())
             t = {k: [] for k in sides}
-            for _ in range(REPS):
+            for _ in range(args.reps):
                 for k, fns in sides.items():
-                    t[k].append(time_calls(fns, ITERS))
+                    t[k].append(time_calls(fns, args.iters))
             stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
             flops = 2.0 * 16 * N * c * c * ((h + 1) // 2) * ((w + 1) // 2)
             nbytes = 4.0 * (2 * N * c * h * w + 9 * c * c)
@@ -127,6 +153,7 @@ def main():
             row = {'where': where, 'cin': c, 'cout': c, 'hw': [h, w], 'launches_per_step': count,
                    'bn_relu_epilogue': epi, 'excluded_in_ops': (c, c) in ops._CONV3X3_NCHW_EXCLUDED,
                    'fused_wins': stat['fused'][2] < stat['parent'][1],
+                   'fused_beats_parent_lib': stat['fused'][2] < stat['parent_lib'][1] if plib is not None else None,
                    'winograd_gflop': round(flops / 1e9, 3), 'algorithmic_MB': round(nbytes / 1e6, 2),
                    'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
                    'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / stat['fused'][0], 3),
@@ -142,7 +169,7 @@ def main():
                       {k: round(v[0], 1) for k, v in stat.items() if k.startswith('form')}, limit_us,
                       row['fused_wins'], maxdiff), flush=True)
             del xs, ys, yp
-    res = {'device': torch.cuda.get_device_name(0), 'iters': ITERS, 'reps': REPS, 'batch': N, 'forms': FORMS,
+    res = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'reps': args.reps, 'batch': N, 'forms': FORMS,
            'classes': rows,
            'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
            'per_step_fused_us': round(sum(r['fused_us'] * r['launches_per_step'] for r in rows), 1)}

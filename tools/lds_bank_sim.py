@@ -13,6 +13,7 @@ and candidate swizzles.  Prints conflict cycles / all cycles (SQ_LDS_BANK_CONFLI
 SQ_LDS_IDX_ACTIVE) per path and set.
 
     python tools/lds_bank_sim.py [--sets bench,voc,train]
+    python tools/lds_bank_sim.py --conv3x3-nchw     the U image of tools/csrc/conv3x3_nchw_lab.hip
 """
 import argparse
 import os
@@ -120,11 +121,41 @@ def item_reads(R, Cs2, lanes, cell_bytes, quad_off, rot=False, steps=4, cell_add
     return reads
 
 
+def write_cycles_b128(addrs):
+    """LDS cycles of one ds_write_b128: 8 groups of 8 contiguous lanes, bank (a / 4) mod 32, a
+    16-B write covers 4 banks (one of 8 slots of a 128-B row)."""
+    tot = 0
+    for g in range(8):
+        slots = {}
+        for ln in range(8 * g, 8 * g + 8):
+            slots.setdefault((addrs[ln] // 16) % 8, set()).add(addrs[ln])
+        tot += max(len(v) for v in slots.values())
+    return tot
+
+
+def conv3x3_nchw():
+    """The laboratory NCHW Winograd forms' U chunk image [cin 16][quad 4][cout 16 NC] of float4:
+    lane (q, t) of step js reads slot ((4 js + q) 4 + i) 16 NC + 16 nc + t; staging thread j of
+    64 TR writes slots j + 64 TR m of each half.  4 cycles per read and 8 per write are the
+    conflict-free costs."""
+    for nc_blocks, tr in ((2, 4), (1, 2), (1, 4)):
+        nco = 16 * nc_blocks
+        rd = [cycles([(((4 * js + (ln >> 4)) * 4 + i) * nco + 16 * nc + (ln & 15)) * 16 for ln in range(64)])
+              for js in range(4) for i in range(4) for nc in range(nc_blocks)]
+        wr = [write_cycles_b128([(h * 32 * nco + m * tr * 64 + w * 64 + ln) * 16 for ln in range(64)])
+              for h in range(2) for m in range(nco // (2 * tr)) for w in range(tr)]
+        print('NC {} TR {}: ds_read_b128 cycles min {} max {} (conflict-free 4); ds_write_b128 cycles min {} max {} '
+              '(conflict-free 8)'.format(nc_blocks, tr, min(rd), max(rd), min(wr), max(wr)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sets', default='bench,voc,train')
     ap.add_argument('--limit', type=int, default=400, help='RoIs per set (a sample)')
+    ap.add_argument('--conv3x3-nchw', action='store_true', help='the U image of the NCHW Winograd LDS forms instead')
     args = ap.parse_args()
+    if args.conv3x3_nchw:
+        return conv3x3_nchw()
     for name in args.sets.split(','):
         path = os.path.join(REPO, 'tests', 'golden', SETS[name])
         if not os.path.exists(path):
