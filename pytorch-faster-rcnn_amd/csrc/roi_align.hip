@@ -2,7 +2,9 @@
 // images.
 // Reference: lib/region.py:243-306 (BasicRoIExtractor: map_rois_to_levels,
 // per-level torchvision RoIAlign(output_size, 1/stride, sampling_ratio=2)),
-// torchvision legacy (aligned=False) RoIAlign semantics.
+// torchvision RoIAlign semantics: the legacy aligned=False every config uses, and aligned=True
+// (half-pixel shift, no clamp of the RoI's size to 1: zero-size RoIs, 0 x 0 adaptive grids) on
+// every kernel below (tests/test_gpu_roi_align_aligned.py).
 //
 // Forward (all bit-identical: -ffp-contract=off, reference op order; kernels in
 // roi_kernels.h, each in the one form dispatched here; the template arguments roi_fwd picks are
@@ -14,7 +16,9 @@
 //  * roi_align_fwd_band_kernel -- channels-last features (unit channel stride, C % 4
 //    == 0, sampling 2, 7x7 bins and smaller): small windows as the quad kernel (16-B
 //    LDS-DMA staging, lane = cell, one ds_read_b128 per tap for 4 channels), larger ones
-//    in row bands of [cell][16 channels] with one 64-B request per cell (roi_kernels.h).
+//    in row bands of [cell][16 channels] with one 64-B request per cell (roi_kernels.h); a
+//    dense window with a bin taller than a band (a RoI several times its level's height) as
+//    tap-list rows.
 //  * roi_align_fwd_quad_kernel -- the quad path alone, for channels-last shapes the band
 //    kernel does not take.
 //  * roi_align_fwd_pair_kernel -- the default (sampling 2, up to 8x8 bins, even C):

@@ -475,7 +475,12 @@ struct PairLane {
 };
 
 // kUnit: bytes of one cell's entry in a slab region (8: a channel pair; 16: a quad).
-template <int kUnit = 8>
+// kBandCells > 0 (the band kernel, which stages windows above 2 * kBandCells cells in bands of
+// whole rows): a dense window in which one bin's two y samples span more rows than a band holds
+// takes the tap-list rows instead, where every bin has its own 4 rows.  Evenly spaced valid
+// samples keep a bin within 5 rows of a dense window (band_fits); a RoI several times taller than
+// its level has few valid samples, far apart, and its window is still dense.
+template <int kUnit = 8, int kBandCells = 0>
 __device__ __forceinline__ void pair_setup(const RoiLevels& lv, const RoiCfg& c, const RoiRaw& raw, int lane,
                                            PairGeom& G, PairLane& P) {
   constexpr int SR = 2;
@@ -506,20 +511,29 @@ __device__ __forceinline__ void pair_setup(const RoiLevels& lv, const RoiCfg& c,
   G.empty = !(y1 >= y0 && x1 >= x0);
   G.y0 = y0;
   G.x0 = x0;
-  const bool dy = y1 - y0 + 1 <= nly, dx = x1 - x0 + 1 <= nlx;
-  G.dy = dy;
+  bool dy = y1 - y0 + 1 <= nly;
+  const bool dx = x1 - x0 + 1 <= nlx;
   G.dx = dx;
-  G.R = dy ? y1 - y0 + 1 : nly;
   G.Cs = dx ? x1 - x0 + 1 : nlx;
   // slab row stride: odd, so the tap reads of a wave spread over the banks
   G.Cs2 = G.Cs | 1;
+  // this lane's bin
+  const int bin = lane < nbins ? lane : 0;
+  const int py = (int)(((uint32_t)bin * ((65536u + (uint32_t)c.pw - 1u) / (uint32_t)c.pw)) >> 16), px = bin - py * c.pw;
+  if constexpr (kBandCells > 0) {
+    if (!G.empty && dy && (y1 - y0 + 1) * G.Cs2 > 2 * kBandCells) {  // a banded dense window (uniform)
+      const Tap a0 = make_tap(pos_y(py, 0), H), a1 = make_tap(pos_y(py, 1), H);
+      const int span = (lane < nbins && a0.valid && a1.valid) ? a1.hi - a0.lo + 1 : 0;  // one valid sample: <= 2 rows
+      if (__builtin_amdgcn_readfirstlane(wave_max_i32(span)) > kBandCells / G.Cs2) dy = false;
+    }
+  }
+  G.dy = dy;
+  G.R = dy ? y1 - y0 + 1 : nly;
   // feature byte offsets of slab row / column `lane`
   P.rsrc = (dy ? y0 + min(lane, G.R - 1) : (yrow >= 0 ? yrow : y0)) * G.sy * 4;
   P.csrc = (dx ? x0 + min(lane, G.Cs - 1) : (xcol >= 0 ? xcol : x0)) * G.sx * 4;
   // this lane's bin: per-sample factors (zeroed for invalid samples: the same products, or +0)
   // and tap bases + row / column deltas
-  const int bin = lane < nbins ? lane : 0;
-  const int py = (int)(((uint32_t)bin * ((65536u + (uint32_t)c.pw - 1u) / (uint32_t)c.pw)) >> 16), px = bin - py * c.pw;
   P.rlo = 0x7fffffff;
   P.rhi = -1;
   P.vmask = 0u;
@@ -1149,7 +1163,7 @@ __device__ __forceinline__ void band_body(const RoiCfg& c, float* __restrict__ o
     const int rs = rmin == 0x7fffffff ? 0 : max(0, rmin);  // only bins without a valid row left: one row
     const int rcap = min(rs + rows_cap, R);
     bool in = pending && P.rhi < rcap;
-    if (!__ballot(in)) in = pending;  // unreachable by the rows bound (host: 5 rows fit); never loops forever
+    if (!__ballot(in)) in = pending;  // unreachable: a bin's rows fit a band (pair_setup<16, kSlabCells>); never loops forever
     const int re = min(R, max(rs + 1, __builtin_amdgcn_readfirstlane(wave_max_i32(in ? P.rhi + 1 : 0))));
     const int nb = (re - rs) * Cs2;
     const int nj = (nb + 15) >> 4;
@@ -1259,7 +1273,7 @@ __device__ __forceinline__ void band_item(const RoiLevels& lv, const RoiCfg& c, 
   PairGeom G;
   PairLane P;
   const RoiRaw raw = roi_fetch(c, k);
-  pair_setup<16>(lv, c, raw, lane, G, P);
+  pair_setup<16, kSlabCells>(lv, c, raw, lane, G, P);
   band_body<kStamp, kSlabCells>(c, out, k, chunk, item, sbase, t_start, lane, G, P);
 }
 
@@ -1302,8 +1316,9 @@ roi_align_fwd_band_kernel(RoiLevels lv, RoiCfg c, float* __restrict__ out) {
 }
 
 // the band kernel's shape limits: a bin's rows (sampling 2: its two y samples' taps, <= 5
-// rows -- dense windows of <= 4 ph rows space the 2 ph samples <= (4 ph - 1) / (2 ph - 1) <= 3
-// rows apart, tap lists give 4) fit a band of the widest window row (4 pw entries, odd stride)
+// rows -- dense windows of <= 4 ph rows space 2 ph valid samples <= (4 ph - 1) / (2 ph - 1) <= 3
+// rows apart, tap lists give 4; a dense window of fewer valid samples farther apart is laid out
+// as tap lists, pair_setup) fit a band of the widest window row (4 pw entries, odd stride)
 constexpr bool band_fits(int ph, int pw, int slab_cells) { return 5 * ((4 * pw) | 1) <= slab_cells; }
 
 // ---------------------------------------------------------------------------
