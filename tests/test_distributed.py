@@ -2,20 +2,13 @@
 code over RCCL).  Ranks own disjoint image shards, meet only at the barrier and the
 max-time all-reduce, and rank 0's value = all ranks' images / slowest rank's time."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+import support
 
 
 def _worker(rank, world, port, q):
@@ -34,7 +27,7 @@ def _worker(rank, world, port, q):
 def test_two_rank_gloo_shards_and_max_time():
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = _port()
+    port = support.free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -9,6 +9,8 @@ import functools
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [
@@ -155,9 +157,7 @@ def test_bn_without_running_statistics_takes_the_modules(dev, monkeypatch):
     conv = torch.nn.Conv2d(16, 64, 1, bias=False).to(dev)
     bn = torch.nn.BatchNorm2d(64, track_running_stats=False).to(dev).eval()
     x = torch.randn(1, 16, 2, 2, device=dev)
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     with torch.no_grad():
         ref = torch.relu(bn(conv(x)))
         assert not ops.conv1x1_fused_ok(conv, bn, x)
@@ -214,27 +214,17 @@ def test_dispatch(dev, monkeypatch):
         x_cl = x.contiguous(memory_format=torch.channels_last)
         # which entries run is read off ops.call; the values are MIOpen's, and two calls of one
         # MIOpen conv need not agree bit for bit (the first call of a shape may take another solver)
-        names = []
-        real_call = ops.call
-        monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+        spy = support.spy_entries(monkeypatch)
         for c, b, xi in ((strided, bn_s, x), (biased, bn_b, x), (conv, bn, x_cl)):
             assert not ops.conv1x1_fused_ok(c, b, xi)
-            del names[:]
+            spy.clear()
             got = ops.conv1x1_bn_act(c, b, xi, relu=False)
-            assert names == ['frh_bn_act']
+            assert spy.names == ['frh_bn_act']
             want = ops.bn_act(c(xi), b, relu=False)
             torch.testing.assert_close(got, want, rtol=1e-3, atol=1e-3 * float(want.abs().max()))
-        del names[:]
+        spy.clear()
         ops.conv1x1_bn_act(conv, bn, x, skip=skip)
-        assert names == ['frh_conv1x1_bn_act']
-
-
-def _bottleneck_unfused(blk, x):
-    from frcnn_amd import ops
-    y = ops.bn_act(blk.conv1(x), blk.bn1)
-    y = ops.bn_act(blk.conv2(y), blk.bn2)
-    skip = ops.bn_act(blk.downsample[0](x), blk.downsample[1], relu=False) if blk.do_downsample else x
-    return ops.bn_act(blk.conv3(y), blk.bn3, skip=skip)
+        assert spy.names == ['frh_conv1x1_bn_act']
 
 
 @pytest.mark.parametrize('args', [(256, 256), (64, 256, True)])
@@ -255,5 +245,5 @@ def test_bottleneck_matches_unfused(dev, args):
         x = torch.randn(2, args[0], 8, 12, device=dev)
         assert ops.conv1x1_fused_ok(blk.conv1, blk.bn1, x)
         y = blk(x)
-        ref = _bottleneck_unfused(blk, x)
+        ref = support.bottleneck_unfused(blk, x)
     torch.testing.assert_close(y, ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max()))

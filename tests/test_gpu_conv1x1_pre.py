@@ -10,6 +10,8 @@ import functools
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 # (n, cin, cout, h, w): the shapes of test_gpu_conv1x1.py
@@ -26,11 +28,6 @@ S2_CHANNELS = [(64, 128), (256, 512)]
 EPS = 1e-5
 
 
-def _bn_params(c, g):
-    gamma = (torch.rand(c, generator=g) + 0.5) * torch.where(torch.rand(c, generator=g) < 0.5, -1.0, 1.0)
-    return gamma, torch.rand(c, generator=g) - 0.5, torch.rand(c, generator=g) * 2 - 1, torch.rand(c, generator=g) * 1.5 + 0.5
-
-
 @functools.lru_cache(maxsize=None)
 def _case(n, cin, cout, h, w, dev):
     """x [n, cin, h, w], the weight, a skip for the plane (h, w) and for its stride-2 output, the
@@ -39,8 +36,8 @@ def _case(n, cin, cout, h, w, dev):
     d = dict(x=torch.randn(n, cin, h, w, generator=g), w=torch.randn(cout, cin, generator=g),
              skip=torch.randn(n, cout, h, w, generator=g),
              skip2=torch.randn(n, cout, (h + 1) // 2, w // 2, generator=g))
-    d['gamma'], d['beta'], d['mean'], d['var'] = _bn_params(cout, g)
-    d['pgamma'], d['pbeta'], d['pmean'], d['pvar'] = _bn_params(cin, g)
+    d['gamma'], d['beta'], d['mean'], d['var'] = support.bn_params(cout, g)
+    d['pgamma'], d['pbeta'], d['pmean'], d['pvar'] = support.bn_params(cin, g)
     return {k: v.to(dev) for k, v in d.items()}
 
 
@@ -137,24 +134,6 @@ def test_stride2_refuses_an_output_width_off_4(dev):
     torch.testing.assert_close(got, want, rtol=1e-3, atol=1e-3 * float(want.abs().max()))
 
 
-def _block(dev, args):
-    from frcnn_amd.backbones import Bottleneck
-    torch.manual_seed(11)
-    blk = Bottleneck(*args).to(dev).eval()
-    for m in blk.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            _randomise_bn(m)
-    return blk, torch.randn(2, args[0], 8, 16, device=dev)
-
-
-def _bottleneck_unfused(blk, x):
-    from frcnn_amd import ops
-    y = ops.bn_act(blk.conv1(x), blk.bn1)
-    y = ops.bn_act(blk.conv2(y), blk.bn2)
-    skip = ops.bn_act(blk.downsample[0](x), blk.downsample[1], relu=False) if blk.do_downsample else x
-    return ops.bn_act(blk.conv3(y), blk.bn3, skip=skip)
-
-
 BLOCKS = [(256, 256), (256, 512, True)]
 
 
@@ -163,13 +142,10 @@ def test_bottleneck_launches_and_values(dev, args, monkeypatch):
     """Under no_grad no frh_bn_act pass is left where both fused paths hold (conv3 reads conv2's
     raw output through the input-side BN, the stride-2 projection is one launch), and the block's
     output is within the tolerance the trunk parity tests grant of the unfused chain."""
-    from frcnn_amd import ops
-    blk, x = _block(dev, args)
-    names = []
-    real_call = ops.call
+    blk, x = support.block(dev, args, _randomise_bn)
     with torch.no_grad():
-        ref = _bottleneck_unfused(blk, x)
-        monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+        ref = support.bottleneck_unfused(blk, x)
+        names = support.spy_entries(monkeypatch).names
         y = blk(x)
     assert 'frh_bn_act' not in names
     assert names.count('frh_conv1x1_bn_act_pre') == 1
@@ -179,14 +155,11 @@ def test_bottleneck_launches_and_values(dev, args, monkeypatch):
 
 @pytest.mark.parametrize('args', BLOCKS)
 def test_bottleneck_under_grad_keeps_the_old_path(dev, args, monkeypatch):
-    from frcnn_amd import ops
-    blk, x = _block(dev, args)
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    blk, x = support.block(dev, args, _randomise_bn)
+    names = support.spy_entries(monkeypatch).names
     with torch.enable_grad():
         y = blk(x)
-        ref = _bottleneck_unfused(blk, x)
+        ref = support.bottleneck_unfused(blk, x)
     assert y.grad_fn is not None
     assert set(names) == {'frh_bn_act'}
     torch.testing.assert_close(y, ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max()))

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [
@@ -25,26 +27,6 @@ SHAPES = [
     (1, 32, 192, 17, 34),   # ragged tile block on both sides, three cout blocks
 ]
 FLAGS = [(b, r) for b in (False, True) for r in (False, True)]
-
-BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float64)
-G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)
-AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64)
-
-
-def _wino_magnitude(x, w):
-    """|A^T| (sum_c (|G||g||G^T|) * (|B^T||d||B|)) |A| in float64: the sum of the magnitudes of
-    every term the algorithm adds up, per output element."""
-    n, cin, h, wd = x.shape
-    ht, wt = (h + 1) // 2, (wd + 1) // 2
-    xp = torch.zeros(n, cin, 2 * ht + 2, 2 * wt + 2, dtype=torch.float64)
-    xp[:, :, 1:h + 1, 1:wd + 1] = x.double().abs()
-    d = xp.unfold(2, 4, 2).unfold(3, 4, 2)  # n, cin, ht, wt, 4, 4
-    va = BT.abs() @ d @ BT.t().abs()
-    ua = G.abs() @ w.double().abs() @ G.t().abs()  # cout, cin, 4, 4
-    ma = torch.einsum('ocab,nchwab->nohwab', ua, va)
-    ya = AT.abs() @ ma @ AT.t().abs()  # n, cout, ht, wt, 2, 2
-    return ya.permute(0, 1, 2, 4, 3, 5).reshape(n, -1, 2 * ht, 2 * wt)[:, :, :h, :wd]
-
 
 @functools.lru_cache(maxsize=None)
 def _case(shape):
@@ -56,7 +38,7 @@ def _case(shape):
     bias = torch.randn(cout, generator=g)
     y64 = F.conv2d(x.double(), wt.double(), None, padding=1)
     y32 = F.conv2d(x, wt, None, padding=1)
-    return dict(x=x, w=wt, bias=bias, y64=y64, y32=y32, mag=_wino_magnitude(x, wt))
+    return dict(x=x, w=wt, bias=bias, y64=y64, y32=y32, mag=support.wino_magnitude(x, wt))
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,14 +221,7 @@ def test_dispatch(dev, monkeypatch):
     from frcnn_amd import ops
     conv = _conv(dev, 64, 128, 3)
     x = torch.randn(2, 64, 8, 12, device=dev).contiguous(memory_format=torch.channels_last)
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
-
-    def ran(fn):
-        del names[:]
-        out = fn()
-        return out, list(names)
+    ran = support.spy_entries(monkeypatch).ran
 
     with torch.enable_grad():
         assert conv.weight.requires_grad and not ops.conv3x3_fused_ok(conv, x)
@@ -323,17 +298,16 @@ def test_fpn_and_rpn_head_match_the_unfused_path(dev, monkeypatch):
                 m.bias.uniform_(-0.5, 0.5)
         feats = [torch.randn(2, c, h, w, device=dev) for c, (h, w) in
                  zip((32, 64, 128, 256), ((38, 52), (19, 26), (10, 13), (5, 7)))]
-        names = []
-        real_call = ops.call
-        monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+        spy = support.spy_entries(monkeypatch)
         levels = fpn(feats)
         cls, reg = head(levels)
-        assert names.count('frh_conv3x3_bias_act_levels') == 2  # the FPN's four output convs, the head's five levels
+        # the FPN's four output convs, the head's five levels
+        assert spy.names.count('frh_conv3x3_bias_act_levels') == 2
         monkeypatch.setattr(ops, 'conv3x3_fused_ok', lambda conv, x, alone=True: False)
-        del names[:]
+        spy.clear()
         ref_levels = fpn(feats)
         ref_cls, ref_reg = head(ref_levels)
-        assert not [n for n in names if n.startswith('frh_conv3x3')]
+        assert not [n for n in spy.names if n.startswith('frh_conv3x3')]
     for got, want in zip(levels + cls + reg, ref_levels + ref_cls + ref_reg):
         assert got.shape == want.shape
         torch.testing.assert_close(got, want, rtol=1e-3, atol=1e-3 * float(want.abs().max()))

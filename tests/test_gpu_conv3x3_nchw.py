@@ -17,15 +17,14 @@ The entry takes no strides, so a non-contiguous x cannot reach it: that case is 
 predicate (test_noncontiguous_x_takes_the_module), the others by the entry itself."""
 import ctypes
 import functools
-import os
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import support
+
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPES = [
     (1, 16, 64, 3, 8),       # smaller than one tile block, odd h, four cin steps
@@ -36,32 +35,6 @@ SHAPES = [
 FORMS = [None, 0, 1, 2]
 EPS = 1e-5
 
-BT = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float64)
-G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64)
-AT = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float64)
-
-
-def _wino_magnitude(x, w):
-    """|A^T| (sum_c (|G||g||G^T|) * (|B^T||d||B|)) |A| in float64 for NCHW x [n, cin, h, w] and
-    w [cout, cin, 3, 3]: the sum of the magnitudes of every term the algorithm adds up, per output
-    element (test_gpu_conv3x3.py's bound; the layout of x and w in memory does not enter)."""
-    n, cin, h, wd = x.shape
-    ht, wt = (h + 1) // 2, (wd + 1) // 2
-    xp = torch.zeros(n, cin, 2 * ht + 2, 2 * wt + 2, dtype=torch.float64)
-    xp[:, :, 1:h + 1, 1:wd + 1] = x.double().abs()
-    d = xp.unfold(2, 4, 2).unfold(3, 4, 2)  # n, cin, ht, wt, 4, 4
-    va = BT.abs() @ d @ BT.t().abs()
-    ua = G.abs() @ w.double().abs() @ G.t().abs()  # cout, cin, 4, 4
-    ma = torch.einsum('ocab,nchwab->nohwab', ua, va)
-    ya = AT.abs() @ ma @ AT.t().abs()  # n, cout, ht, wt, 2, 2
-    return ya.permute(0, 1, 2, 4, 3, 5).reshape(n, -1, 2 * ht, 2 * wt)[:, :, :h, :wd]
-
-
-def _bn_params(c, g):
-    gamma = (torch.rand(c, generator=g) + 0.5) * torch.where(torch.rand(c, generator=g) < 0.5, -1.0, 1.0)
-    return gamma, torch.rand(c, generator=g) - 0.5, torch.rand(c, generator=g) * 2 - 1, torch.rand(c, generator=g) * 1.5 + 0.5
-
-
 @functools.lru_cache(maxsize=None)
 def _case(shape):
     """Inputs (CPU f32) and the references of one shape, computed once."""
@@ -69,22 +42,16 @@ def _case(shape):
     g = torch.Generator().manual_seed(4000 + cin + 7 * cout + h * w)
     x = torch.randn(n, cin, h, w, generator=g)
     wt = torch.randn(cout, cin, 3, 3, generator=g)
-    bn = _bn_params(cout, g)
+    bn = support.bn_params(cout, g)
     y64 = F.conv2d(x.double(), wt.double(), None, padding=1)
     y32 = F.conv2d(x, wt, None, padding=1)
-    return dict(x=x, w=wt, bn=bn, y64=y64, y32=y32, mag=_wino_magnitude(x, wt))
+    return dict(x=x, w=wt, bn=bn, y64=y64, y32=y32, mag=support.wino_magnitude(x, wt))
 
 
 @functools.lru_cache(maxsize=None)
 def _on_dev(shape, dev):
     c = _case(shape)
     return dict(x=c['x'].to(dev), w=c['w'].to(dev), bn=[t.to(dev) for t in c['bn']])
-
-
-def _tools():
-    sys.path.insert(0, os.path.join(REPO, 'tools'))
-    import toolslib
-    return toolslib.load()
 
 
 def _fused(x, w, bn=None, relu=False, form=None, y=None, ws=None, n=None):
@@ -102,7 +69,7 @@ def _fused(x, w, bn=None, relu=False, form=None, y=None, ws=None, n=None):
     if form is None:
         _lib.call('frh_conv3x3_nchw_bn_act', *a)
     else:
-        st = _tools().frh_conv3x3_nchw_bn_act_form(form, *a)
+        st = support.tools().frh_conv3x3_nchw_bn_act_form(form, *a)
         assert st == 0, _lib.load().frh_last_error()
     return y
 
@@ -207,8 +174,9 @@ def test_entry_refuses_what_it_cannot_run(dev):
     # the form with two channel blocks needs cout % 32 == 0
     w48 = torch.zeros(48, 16, 3, 3, device=dev)
     y48 = torch.full((1, 48, 4, 8), 7.0, device=dev)
-    assert _tools().frh_conv3x3_nchw_bn_act_form(1, p(x), p(w48), None, None, None, None, 0.0, p(y48), p(big), 1, 16, 48,
-                                                 4, 8, 0, _lib.stream_of(x)) != 0
+    form1 = support.tools().frh_conv3x3_nchw_bn_act_form
+    assert form1(1, p(x), p(w48), None, None, None, None, 0.0, p(y48), p(big), 1, 16, 48, 4, 8, 0,
+                 _lib.stream_of(x)) != 0
     assert bool((y48 == 7.0).all())
     assert torch.equal(_fused(x, w48, y=y48), torch.zeros_like(y48))  # the product entry picks a form that fits
 
@@ -233,18 +201,6 @@ def _randomise_bn(bn):
         bn.running_var.uniform_(0.5, 2.0)
 
 
-def _recorded(ops, monkeypatch):
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
-
-    def ran(fn):
-        del names[:]
-        out = fn()
-        return out, list(names)
-    return ran
-
-
 def test_dispatch(dev, monkeypatch):
     """With the table empty the op is the fused entry under no_grad; with the table full, with
     grad mode on (whether or not a gradient is needed), for a stride-2 conv, a biased conv, a training-mode BN and CPU tensors it is
@@ -255,7 +211,7 @@ def test_dispatch(dev, monkeypatch):
     bn = torch.nn.BatchNorm2d(64).to(dev).eval()
     _randomise_bn(bn)
     x = torch.randn(2, 64, 8, 12, device=dev)
-    ran = _recorded(ops, monkeypatch)
+    ran = support.spy_entries(monkeypatch).ran
     bnp = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
     full = frozenset([(64, 64), (128, 128), (256, 256), (512, 512)])
 
@@ -317,24 +273,6 @@ def test_dispatch(dev, monkeypatch):
         assert got == [] and torch.equal(y, cpu_conv(x_cpu).relu())
 
 
-def _block(dev, args):
-    from frcnn_amd.backbones import Bottleneck
-    torch.manual_seed(11)
-    blk = Bottleneck(*args).to(dev).eval()
-    for m in blk.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            _randomise_bn(m)
-    return blk, torch.randn(2, args[0], 8, 16, device=dev)
-
-
-def _bottleneck_unfused(blk, x):
-    from frcnn_amd import ops
-    y = ops.bn_act(blk.conv1(x), blk.bn1)
-    y = ops.bn_act(blk.conv2(y), blk.bn2)
-    skip = ops.bn_act(blk.downsample[0](x), blk.downsample[1], relu=False) if blk.do_downsample else x
-    return ops.bn_act(blk.conv3(y), blk.bn3, skip=skip)
-
-
 @pytest.mark.parametrize('args', [(256, 256), (2048, 2048)])
 def test_bottleneck_with_conv2_dispatched(dev, args, monkeypatch):
     """With conv2's class dispatched, Bottleneck(256, 256) (conv3 takes bn2 on its input side:
@@ -344,12 +282,12 @@ def test_bottleneck_with_conv2_dispatched(dev, args, monkeypatch):
     (2048 -> 512) is one of the 1x1 kernel's own exclusions and would record its frh_bn_act, so
     that table is emptied here: then the block records no frh_bn_act at all."""
     from frcnn_amd import ops
-    blk, x = _block(dev, args)
+    blk, x = support.block(dev, args, _randomise_bn)
     monkeypatch.setattr(ops, '_CONV3X3_NCHW_EXCLUDED', frozenset())
     monkeypatch.setattr(ops, '_CONV1X1_EXCLUDED', frozenset())
-    ran = _recorded(ops, monkeypatch)
+    ran = support.spy_entries(monkeypatch).ran
     with torch.no_grad():
-        ref = _bottleneck_unfused(blk, x)
+        ref = support.bottleneck_unfused(blk, x)
         y, names = ran(lambda: blk(x))
     assert names.count('frh_conv3x3_nchw_bn_act') == 1 and 'frh_bn_act' not in names
     assert names.count('frh_conv1x1_bn_act_pre') == (1 if args[0] == 256 else 0)

@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_conv3x3_nchw import EPS, _case, _fused, _on_dev, _tools  # noqa: E402
+import support  # noqa: E402
+from test_gpu_conv3x3_nchw import EPS, _case, _fused, _on_dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +51,8 @@ def _refused(shape, form, dev):
     y = torch.full((n, cout, h, w), 7.0, device=dev)
     ws = torch.empty(16 * cin * cout, device=dev)
     p = _lib.ptr
-    st = _tools().frh_conv3x3_nchw_bn_act_form(form, p(d['x']), p(d['w']), None, None, None, None, 0.0, p(y), p(ws), n, cin,
-                                               cout, h, w, 0, _lib.stream_of(y))
+    st = support.tools().frh_conv3x3_nchw_bn_act_form(form, p(d['x']), p(d['w']), None, None, None, None, 0.0, p(y),
+                                                      p(ws), n, cin, cout, h, w, 0, _lib.stream_of(y))
     torch.cuda.synchronize()
     assert st != 0
     assert bool((y == 7.0).all())

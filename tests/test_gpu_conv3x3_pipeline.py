@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 CL = torch.channels_last
@@ -29,18 +31,14 @@ BIT_SHAPES = [(2, 64, 64, 19, 32), (2, 256, 128, 10, 16), (1, 32, 192, 17, 34)]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv3x3_bits.json')
 
 
-def _ints(g, lo, hi, *size):
-    return torch.randint(lo, hi + 1, size, generator=g).float()
-
-
 @functools.lru_cache(maxsize=None)
 def _int_case(shape):
     """Integer inputs (CPU f32) and the float64 convolution without bias, computed once."""
     n, cin, cout, h, w = shape
     g = torch.Generator().manual_seed(7000 + cin + 7 * cout + h * w)
-    x = _ints(g, -3, 3, n, cin, h, w)
-    wt = 4.0 * _ints(g, -2, 2, cout, cin, 3, 3)
-    bias = _ints(g, -5, 5, cout)
+    x = support.ints(g, -3, 3, n, cin, h, w)
+    wt = 4.0 * support.ints(g, -2, 2, cout, cin, 3, 3)
+    bias = support.ints(g, -5, 5, cout)
     return dict(x=x, w=wt, bias=bias, y64=F.conv2d(x.double(), wt.double(), None, padding=1))
 
 
@@ -92,10 +90,10 @@ def test_levels_launch_is_exact_and_equals_single_launches(dev, bias, relu, shar
     from frcnn_amd import _lib
     n, cin, cout = 2, 40, 128
     g = torch.Generator().manual_seed(7100 + shared)
-    xs_c = [_ints(g, -3, 3, n, cin, h, w) for h, w in ((6, 10), (3, 5), (2, 3))]
-    ws_c = [4.0 * _ints(g, -2, 2, cout, cin, 3, 3) for _ in range(1 if shared else 3)]
+    xs_c = [support.ints(g, -3, 3, n, cin, h, w) for h, w in ((6, 10), (3, 5), (2, 3))]
+    ws_c = [4.0 * support.ints(g, -2, 2, cout, cin, 3, 3) for _ in range(1 if shared else 3)]
     ws_c = ws_c * 3 if shared else ws_c
-    bs_c = [_ints(g, -5, 5, cout) for _ in range(3)]
+    bs_c = [support.ints(g, -5, 5, cout) for _ in range(3)]
     xs = [x.to(dev).contiguous(memory_format=CL) for x in xs_c]
     wd = [w.to(dev).contiguous(memory_format=CL) for w in (ws_c[:1] if shared else ws_c)]
     wd = wd * 3 if shared else wd

@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 CL = torch.channels_last
@@ -38,14 +40,10 @@ def cases_bound(cin):
     return X_MAX * W_MAX * 9 * cin + BIAS_MAX
 
 
-def _ints(g, lo, hi, *size):
-    return torch.randint(lo, hi + 1, size, generator=g).float()
-
-
 def _draw(g, n, cin, cout, hws):
-    xs = [_ints(g, -X_MAX, X_MAX, n, cin, h, w) for h, w in hws]
-    wt = 4.0 * _ints(g, -2, 2, cout, cin, 3, 3)
-    bias = _ints(g, -BIAS_MAX, BIAS_MAX, cout)
+    xs = [support.ints(g, -X_MAX, X_MAX, n, cin, h, w) for h, w in hws]
+    wt = 4.0 * support.ints(g, -2, 2, cout, cin, 3, 3)
+    bias = support.ints(g, -BIAS_MAX, BIAS_MAX, cout)
     return xs, wt, bias
 
 

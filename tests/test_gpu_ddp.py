@@ -34,24 +34,17 @@ in-process replays of the same calls are bit-identical under poisoned workspaces
 import copy
 import hashlib
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 STEPS = 2
 WORLD = 2
-
-
-def _port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _reference_step(model, cfg, batch, world, seed):
@@ -134,7 +127,7 @@ def test_ddp_two_gloo_ranks_on_one_gpu(dev, config):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = _port()
+    port = support.free_port()
     procs = [ctx.Process(target=_worker, args=(r, WORLD, port, q, config)) for r in range(WORLD)]
     for p in procs:
         p.start()

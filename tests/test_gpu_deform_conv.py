@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import ga_inputs
+import support
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -74,12 +75,10 @@ def test_strided_view_runs_without_a_copy(dev, monkeypatch):
     from frcnn_amd import ops
     (xh, _, _), (xb, _, _) = _inputs(dev, 2, 32, 64, 4, 9, 13, seed=23)
     host, (_, off, wt) = _inputs(dev, 2, 32, 64, 4, 5, 7, seed=24)
-    seen = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (seen.append((name, a[0].value)), real(name, *a))[1])
+    spy = support.spy_entries(monkeypatch)
     view = xb[:, :, ::2, ::2]
     y = ops.deform_conv3x3(view, off, wt, 4)
-    assert seen == [('frh_deform_conv3x3_act', xb.data_ptr())]
+    assert [(name, a[0].value) for name, a in spy.calls] == [('frh_deform_conv3x3_act', xb.data_ptr())]
     _check(y, [xh[:, :, ::2, ::2], host[1], host[2]], 4)
     assert torch.equal(y, ops.deform_conv3x3(view.contiguous(memory_format=torch.channels_last), off, wt, 4))
 
@@ -163,9 +162,7 @@ def test_levels_equal_the_per_level_calls(dev, monkeypatch):
     big = torch.randn(2, 32, 3, 3, generator=torch.Generator().manual_seed(33)).to(dev) \
         .contiguous(memory_format=torch.channels_last)
     xs[4] = big[:, :, ::2, ::2]  # the last level as a stride-2 view
-    names = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     ge = ops.deform_conv3x3_levels(xs, ss, wt, 4, relu=True, offset_weight=ow)
     ex = ops.deform_conv3x3_levels(xs, offs, wt, 4, relu=True)
     assert names == ['frh_deform_conv3x3_act_levels'] * 2
@@ -226,9 +223,7 @@ def test_dispatch(dev, monkeypatch):
     no library call, and gives its result; the module's backward runs."""
     from frcnn_amd import ops
     from frcnn_amd.dcn import DeformConv
-    names = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     host, (x, off, wt) = _inputs(dev, 2, 32, 64, 4, 5, 7, seed=35)
     m = DeformConv(32, 64, 3, padding=1, deformable_groups=4).to(dev)
     assert [k for k, _ in m.named_parameters()] == ['weight'] and m.weight.shape == (64, 32, 3, 3)

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import fcos_inputs
+import support
 
 pytestmark = pytest.mark.gpu
 TAGS = sorted(fcos_inputs.LOSS_CASES)
@@ -169,10 +170,6 @@ def _dev_case(c, dev, grad=False):
     return outs + [torch.from_numpy(c[k]).to(dev) for k in ('labels', 'ltrb', 'ctr_t')]
 
 
-def _losses(out):
-    return np.array([float(o.detach()) for o in out[:3]])
-
-
 def _grads(out, leaves, scale):
     """(d cls_loss / d cls, d bbox_loss / d reg, d ctr_loss / d ctr), each loss on its own with the
     upstream gradient `scale`; the six other pairs must be exactly zero."""
@@ -202,7 +199,7 @@ def _cpu_reference(tag):
         for i in range(3):
             g = torch.autograd.grad(out[i], outs[i], retain_graph=True, allow_unused=True)[0]
             grads.append((torch.zeros_like(outs[i]) if g is None else g).numpy() * n)
-        _CPU_REF[tag] = (_losses(out), int(out[3]), grads)
+        _CPU_REF[tag] = (support.loss_values(out), int(out[3]), grads)
     return _CPU_REF[tag]
 
 
@@ -213,9 +210,9 @@ def test_forward_vs_reference_f64(dev, golden, tag):
     c = fcos_inputs.loss_case(tag)
     out = ops.fcos_losses(*_dev_case(c, dev), **fcos_inputs.loss_kwargs(c))
     assert all(o.dim() == 0 and o.is_cuda for o in out)
-    print(tag, _losses(out), z[tag + '_f64'])
+    print(tag, support.loss_values(out), z[tag + '_f64'])
     assert int(out[3]) == int(z[tag + '_num_pos'])
-    np.testing.assert_allclose(_losses(out), z[tag + '_f64'], **LOSS_TOL)
+    np.testing.assert_allclose(support.loss_values(out), z[tag + '_f64'], **LOSS_TOL)
 
 
 @pytest.mark.parametrize('tag', REF_TAGS)
@@ -246,7 +243,7 @@ def test_cases_the_reference_cannot_run_vs_restatement_f64(dev, tag):
     c = fcos_inputs.loss_case(tag)
     t = _dev_case(c, dev, grad=True)
     out = ops.fcos_losses(*t, **fcos_inputs.loss_kwargs(c))
-    got = _losses(out)
+    got = support.loss_values(out)
     print(tag, got, ref_losses, int(out[3]), ref_n)
     assert int(out[3]) == ref_n == {'one': 1, 'no_pos': 0, 'ignored': 0}[tag] and np.isfinite(got).all()
     np.testing.assert_allclose(got, ref_losses, **LOSS_TOL)
@@ -331,11 +328,11 @@ def test_status_word_gives_nan_losses(dev):
     try:
         word.fill_(4)
         out = ops.fcos_losses(*args, **fcos_inputs.loss_kwargs(c))
-        assert np.isnan(_losses(out)).all()
+        assert np.isnan(support.loss_values(out)).all()
     finally:
         word.zero_()
     out = ops.fcos_losses(*args, **fcos_inputs.loss_kwargs(c))
-    assert np.isfinite(_losses(out)).all()
+    assert np.isfinite(support.loss_values(out)).all()
     ops.check_device_status(dev)
 
 
@@ -364,16 +361,6 @@ def test_head_routes_both_samplers_to_the_fused_loss(dev, monkeypatch):
     assert calls == [1, 1]
 
 
-def _no_sync(fn):
-    """fn() with PyTorch's sync debug mode raising on every device-to-host synchronisation."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode('error')
-    try:
-        return fn()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
-
-
 def test_no_host_sync(dev):
     """ops.fcos_assign, ops.fcos_losses (forward and backward) and the head's fused forward_train
     read nothing back to the host; the mode itself is checked to catch the read the old path made."""
@@ -383,13 +370,13 @@ def test_no_host_sync(dev):
     t = _dev_case(c, dev, grad=True)
     ops.fcos_losses(*t, **kw)  # workspace and status word exist from here on
     with pytest.raises(RuntimeError):
-        _no_sync(lambda: int((t[3] > 0).sum()))
+        support.no_sync(lambda: int((t[3] > 0).sum()))
 
     def fused():
         out = ops.fcos_losses(*t, **kw)
         sum(out[:3]).backward()
         return out
-    _no_sync(fused)
+    support.no_sync(fused)
 
     torch.manual_seed(3)
     head = _head(dev, reg_coef_trainable=True)
@@ -406,7 +393,7 @@ def test_no_host_sync(dev):
         sum(losses.values()).backward()
         return losses
     step()  # the convolutions choose their algorithms on the first call
-    losses = _no_sync(step)
+    losses = support.no_sync(step)
     assert list(losses) == ['cls_loss', 'ctr_loss', 'bbox_loss']
     assert all(torch.isfinite(v).item() for v in losses.values())
     assert float(head.reg_coef.grad.abs().sum()) > 0 and float(head.fcos_center.weight.grad.abs().sum()) > 0

@@ -28,23 +28,14 @@
   sets and counts equal; the workspace's zero region is zero after every call.  The sampler's
   definition is pinned by test_gpu_parity.py's numpy restatement (test_device_sampler_*).
 """
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import inputs
+import support
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _tools():
-    sys.path.insert(0, os.path.join(REPO, 'tools'))
-    import toolslib
-    return toolslib.load()
 
 
 def _scores(case, rng, c):
@@ -78,7 +69,7 @@ def _run(dev, case, cls_ch, nhwc, batch, min_size, pre, post, mx, seed, other='f
     if nhwc:
         cls = [c.contiguous(memory_format=torch.channels_last) for c in cls]
         reg = [r.contiguous(memory_format=torch.channels_last) for r in reg]
-    lib = _tools()
+    lib = support.tools()
     args = (cls, reg, anchors, 3, cls_ch, [0.0] * 4, [1.0] * 4, [(600.0, 1000.0)] * batch, [min_size] * batch,
             pre, post, mx, 0.7)
     fused = [ops.rpn_proposals(*args) for _ in range(3)]
@@ -161,7 +152,7 @@ def test_sampler_one_launch_equals_two_launches(dev, S, n, nums, max_num, pos_nu
     three calls in a row with different draws on one workspace (its zero region is left
     zero by every call)."""
     from frcnn_amd import ops
-    lib = _tools()
+    lib = support.tools()
     rng = np.random.default_rng(S * 7 + n)
     num = torch.tensor(nums if nums else [n] * S, dtype=torch.int32, device=dev)
     for call in range(3):
@@ -194,7 +185,7 @@ def test_sampler_workspace_reuse_across_num_segs_and_paths(dev):
     is the same for every S (frh_sample_zero_bytes), so the S = 4 call equals one on a fresh
     workspace."""
     from frcnn_amd import ops
-    lib = _tools()
+    lib = support.tools()
     rng = np.random.default_rng(11)
     n = 40000
     lab2 = torch.from_numpy(rng.choice([0, 1, 2], size=(2, n), p=[0.2, 0.4, 0.4]).astype(np.int64)).to(dev)
@@ -227,7 +218,7 @@ def test_sampler_window_fast_path(dev, n, max_num, pos_num, p, fast):
     holds the selection, and the histogram phases otherwise (stamp 9 of every workgroup of the
     tools timing build); either way the result equals the keys + collect launches."""
     from frcnn_amd import ops, _lib
-    lib = _tools()
+    lib = support.tools()
     S = 2
     rng = np.random.default_rng(n + max_num)
     lab = torch.from_numpy(_labels(rng, S, n, p)).to(dev)

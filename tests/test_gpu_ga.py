@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import ga_inputs
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -148,23 +149,20 @@ def test_guided_anchor_eval_takes_the_fused_levels_entry(dev, monkeypatch):
     """A 64-channel GuidedAnchor in eval mode: one frh_deform_conv3x3_act_levels call, equal (f32
     bar of test_gpu_deform_conv.py's dispatch test) to the same module's training path, which
     takes the restatement and back-propagates into the shape branch's offset layer."""
-    from frcnn_amd import ops
     from frcnn_amd.heads import GARPNHead
     torch.manual_seed(3)
     head = GARPNHead(in_channels=64, feat_channels=64, anchor_strides=list(ga_inputs.STRIDES)).to(dev)
     head.init_weights()
     feats = [torch.randn(2, 64, h, w, device=dev).contiguous(memory_format=torch.channels_last) for h, w in ga_inputs.GRIDS]
-    names = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    spy = support.spy_entries(monkeypatch)
     head.eval()
     with torch.no_grad():
         ev = head.guided_anchor(feats)
-    assert names.count('frh_deform_conv3x3_act_levels') == 1
-    del names[:]
+    assert spy.names.count('frh_deform_conv3x3_act_levels') == 1
+    spy.clear()
     head.train()
     tr = head.guided_anchor(feats)
-    assert not [n for n in names if 'deform' in n]
+    assert not [n for n in spy.names if 'deform' in n]
     for a, b in zip(ev[2], tr[2]):
         torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5)
     sum(t.sum() for t in tr[2]).backward()

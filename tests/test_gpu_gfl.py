@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import gfl_inputs
+import support
 
 pytestmark = pytest.mark.gpu
 TAGS = sorted(gfl_inputs.LOSS_CASES)
@@ -26,10 +27,6 @@ def _dev_case(c, dev, grad=False):
     cls = torch.from_numpy(c['cls']).to(dev).requires_grad_(grad)
     reg = torch.from_numpy(c['reg']).to(dev).requires_grad_(grad)
     return cls, reg, torch.from_numpy(c['labels']).to(dev), torch.from_numpy(c['ltrb']).to(dev)
-
-
-def _losses(out):
-    return np.array([float(o.detach()) for o in out[:3]])
 
 
 def _grads(out, cls, reg, scale):
@@ -57,7 +54,7 @@ def _cpu_reference(c):
         leaf = (cls, reg)[wrt]
         g = torch.autograd.grad(out[i], leaf, retain_graph=True, allow_unused=True)[0]
         grads.append((torch.zeros_like(leaf) if g is None else g).numpy() * n)
-    return _losses(out), int(out[3]), grads
+    return support.loss_values(out), int(out[3]), grads
 
 
 @pytest.mark.parametrize('tag', TAGS)
@@ -67,9 +64,9 @@ def test_forward_vs_reference_f64(dev, golden, tag):
     c = gfl_inputs.loss_case(tag)
     out = ops.gfl_losses(*_dev_case(c, dev), **gfl_inputs.loss_kwargs(c))
     assert all(o.dim() == 0 and o.is_cuda for o in out)
-    print(tag, _losses(out), z[tag + '_f64'])
+    print(tag, support.loss_values(out), z[tag + '_f64'])
     assert int(out[3]) == int(z[tag + '_num_pos'])
-    np.testing.assert_allclose(_losses(out), z[tag + '_f64'], **LOSS_TOL)
+    np.testing.assert_allclose(support.loss_values(out), z[tag + '_f64'], **LOSS_TOL)
 
 
 @pytest.mark.parametrize('tag', TAGS)
@@ -161,9 +158,9 @@ def test_large_forward_and_backward_vs_restatement_f64(dev, large_case):
     assert c['M'] > 256 * 256 and 400 < ref_n < 1000
     cls, reg, labels, ltrb = _dev_case(c, dev, grad=True)
     out = ops.gfl_losses(cls, reg, labels, ltrb, **gfl_inputs.loss_kwargs(c))
-    print(_losses(out), ref_losses, int(out[3]), ref_n)
+    print(support.loss_values(out), ref_losses, int(out[3]), ref_n)
     assert int(out[3]) == ref_n
-    np.testing.assert_allclose(_losses(out), ref_losses, **LOSS_TOL)
+    np.testing.assert_allclose(support.loss_values(out), ref_losses, **LOSS_TOL)
     for g, ref, key in zip(_grads(out, cls, reg, ref_n), ref_grads, ('cls', 'dfl', 'bbox')):
         np.testing.assert_allclose(g.cpu().numpy(), ref, err_msg=key, **GRAD_TOL)
 
@@ -176,7 +173,7 @@ def test_zero_positives(dev):
     assert ref_n == 0
     cls, reg, labels, ltrb = _dev_case(c, dev, grad=True)
     out = ops.gfl_losses(cls, reg, labels, ltrb, **gfl_inputs.loss_kwargs(c))
-    got = _losses(out)
+    got = support.loss_values(out)
     assert int(out[3]) == 0 and np.isfinite(got).all() and got[1] == 0.0 and got[2] == 0.0
     np.testing.assert_allclose(got[0], ref_losses[0], **LOSS_TOL)  # divided by max(num_pos, 1)
     g = _grads(out, cls, reg, 1.0)
@@ -204,8 +201,8 @@ def test_top_bin_target(dev):
     cls, reg, labels, ltrb = _dev_case(c, dev, grad=True)
     assert reg.shape[0] == 4 * bins and reg.is_contiguous()
     out = ops.gfl_losses(cls, reg, labels, ltrb, **gfl_inputs.loss_kwargs(c))
-    assert int(out[3]) == 2 and np.isfinite(_losses(out)).all()
-    np.testing.assert_allclose(_losses(out), ref_losses, **LOSS_TOL)
+    assert int(out[3]) == 2 and np.isfinite(support.loss_values(out)).all()
+    np.testing.assert_allclose(support.loss_values(out), ref_losses, **LOSS_TOL)
     for g, ref, key in zip(_grads(out, cls, reg, ref_n), ref_grads, ('cls', 'dfl', 'bbox')):
         assert torch.isfinite(g).all(), key
         np.testing.assert_allclose(g.cpu().numpy(), ref, err_msg=key, **GRAD_TOL)
@@ -228,11 +225,11 @@ def test_status_word_gives_nan_losses(dev):
     try:
         word.fill_(4)
         out = ops.gfl_losses(*args, **gfl_inputs.loss_kwargs(c))
-        assert np.isnan(_losses(out)).all()
+        assert np.isnan(support.loss_values(out)).all()
     finally:
         word.zero_()
     out = ops.gfl_losses(*args, **gfl_inputs.loss_kwargs(c))
-    assert np.isfinite(_losses(out)).all()
+    assert np.isfinite(support.loss_values(out)).all()
     ops.check_device_status(dev)
 
 
@@ -262,16 +259,6 @@ def test_decode_vs_reference_f64(dev, golden, layout):
     assert E > 0 and err <= 4 * E, (err, E)
 
 
-def _no_sync(fn):
-    """fn() with PyTorch's sync debug mode raising on every device-to-host synchronisation."""
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode('error')
-    try:
-        return fn()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
-
-
 def test_no_host_sync(dev):
     """ops.gfl_losses (forward and backward) and the fused FCOSHead.calc_loss_flat read nothing
     back to the host; the mode itself is checked to catch the read the old path made."""
@@ -282,13 +269,13 @@ def test_no_host_sync(dev):
     cls, reg, labels, ltrb = _dev_case(c, dev, grad=True)
     ops.gfl_losses(cls, reg, labels, ltrb, **kw)  # workspace and status word exist from here on
     with pytest.raises(RuntimeError):
-        _no_sync(lambda: int((labels > 0).sum()))
+        support.no_sync(lambda: int((labels > 0).sum()))
 
     def fused():
         out = ops.gfl_losses(cls, reg, labels, ltrb, **kw)
         sum(out[:3]).backward()
         return out
-    out = _no_sync(fused)
+    out = support.no_sync(fused)
     head = FCOSHead(num_classes=21, in_channels=8, stacked_convs=1, feat_channels=8, reg_std=c['reg_std'],
                     reg_mean=c['reg_mean'], atss_cfg=dict(topk=9, scale=8),
                     loss_cls=dict(type='QualityFocalLoss', use_sigmoid=True, loss_weight=w['cls_weight']),
@@ -297,7 +284,7 @@ def test_no_host_sync(dev):
                                   loss_weight=w['dfl_weight']))
     m = c['M']
     zeros1, zeros = torch.zeros(1, m, device=dev), torch.zeros(m, device=dev)
-    res = _no_sync(lambda: head.calc_loss_flat(cls, reg, zeros1, labels, ltrb, zeros))
+    res = support.no_sync(lambda: head.calc_loss_flat(cls, reg, zeros1, labels, ltrb, zeros))
     assert list(res) == ['cls_loss', 'dfl_loss', 'bbox_loss']
     for v, r in zip(res.values(), out[:3]):
         assert torch.equal(v.detach(), r.detach())

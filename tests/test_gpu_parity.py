@@ -4,7 +4,6 @@ golden vectors and the CPU oracle, on the same seeded inputs.
 Bars: bit-exact for anchors, masks, IoU tables, assignment labels/IoUs,
 sampling (numpy-parity mode), chosen indices and NMS keep lists; float
 tolerances are stated per test (encode/decode log/exp, RoIAlign 1e-5)."""
-import hashlib
 import os
 
 import numpy as np
@@ -13,22 +12,15 @@ import torch
 
 import inputs
 import oracle
+import support
+from support import canon_ties, sha
 
 pytestmark = pytest.mark.gpu
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def T(a, dev, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     return t if dtype is None else t.to(dtype)
-
-
-def canon_ties(boxes, scores):
-    order = np.lexsort((boxes[3], boxes[2], boxes[1], boxes[0], -scores.astype(np.float64)))
-    return boxes[:, order]
 
 
 ANCHOR_CASES = {
@@ -708,15 +700,6 @@ def test_roi_rows_flat_and_batched(dev, golden):
     assert lv1 is None and np.array_equal(rois1.cpu().numpy()[:, 1:], r.T)
 
 
-def _rois(seed, n, batch):
-    b = inputs.random_boxes(seed, n, min_wh=1.0, max_wh=500.0)
-    b[:, :8] = np.array([[-20, -20, 10, 10], [990, 590, 1200, 700], [0, 0, 0, 0], [5, 5, 5.5, 5.2],
-                         [998.9, 598.9, 999, 599], [-300, -300, -200, -100], [0, 0, 999, 599],
-                         [100.25, 200.75, 101.0, 260.5]], np.float32).T
-    bi = np.random.default_rng(seed + 1).integers(0, batch, n).astype(np.float32)
-    return np.concatenate([bi[None], b], 0).T.copy()
-
-
 @pytest.mark.parametrize('layout', ['nchw', 'nhwc'])
 def test_roi_align_forward_default_vs_oracle_p2(dev, layout):
     """The product forward on P2-sized maps, 600 RoIs incl. border / degenerate / outside ones,
@@ -726,7 +709,7 @@ def test_roi_align_forward_default_vs_oracle_p2(dev, layout):
     from frcnn_amd import ops
     grids = [(152, 256), (76, 128), (38, 64), (19, 32)]
     feats = inputs.feature_maps(42, grids, 96, 2)
-    rois = _rois(43, 600, 2)
+    rois = support.rois(43, 600, 2)
     levels = oracle.roi_level_map(rois, 56.0, 4)
     scales = [1 / 4, 1 / 8, 1 / 16, 1 / 32]
     ref = oracle.roi_align(feats, rois, levels, scales, (7, 7), 2)
@@ -773,7 +756,7 @@ def test_roi_align_multilevel_vs_oracle(dev, layout, sampling):
     from frcnn_amd import ops
     grids = [(76, 128), (38, 64), (19, 32), (10, 16)]
     feats = inputs.feature_maps(40, grids, 64, 2)
-    rois = _rois(41, 300, 2)
+    rois = support.rois(41, 300, 2)
     levels = oracle.roi_level_map(rois, 56.0, 4)
     scales = [1 / 8, 1 / 16, 1 / 32, 1 / 64]
     ref = oracle.roi_align(feats, rois, levels, scales, (7, 7), sampling)
@@ -782,18 +765,6 @@ def test_roi_align_multilevel_vs_oracle(dev, layout, sampling):
         ft = [f.contiguous(memory_format=torch.channels_last) for f in ft]
     out = ops.roi_align_multilevel(ft, T(rois, dev), T(levels, dev), scales, (7, 7), sampling).cpu().numpy()
     np.testing.assert_array_equal(out, ref)  # every forward kernel keeps the oracle's operation order
-
-
-def _pathological_rois(batch):
-    """RoIs whose dense tap windows defeat row bands: far larger than a 10 x 30 level, so one bin
-    row's two samples lie 3.6 rows apart with every row between them inside the window (the
-    channel-group kernel stages such a bin row as its 4 tap-list rows), plus RoIs hanging off
-    every edge, tiny and degenerate ones."""
-    r = np.array([[0, 0, 0, 400, 200], [1, -50, -40, 380, 230], [0, 3, 2, 900, 60], [1, 100, 0, 119.5, 300],
-                  [0, -500, -500, 600, 600], [1, 0, 30, 119, 36], [0, 60, 10, 61, 11], [1, 119, 39, 119, 39],
-                  [0, -30, -30, -1, -1], [1, 10, -10, 110, 45], [0, 0, 0, 1000, 200]], np.float32)
-    r[:, 0] %= batch
-    return r
 
 
 @pytest.mark.parametrize('pooled,C', [((7, 7), 64), ((7, 7), 192), ((4, 5), 128), ((8, 8), 64), ((1, 1), 64)])
@@ -809,7 +780,7 @@ def test_roi_align_channel_group_kernel_vs_oracle(dev, pooled, C):
     from frcnn_amd import ops
     grids = [(76, 128), (38, 64), (19, 32), (10, 30)]
     feats = inputs.feature_maps(60, grids, C, 2)
-    rois = np.concatenate([_rois(61, 300, 2), _pathological_rois(2)], 0)
+    rois = np.concatenate([support.rois(61, 300, 2), support.pathological_rois(2)], 0)
     levels = oracle.roi_level_map(rois, 56.0, 4)
     levels[-11:] = 3  # the pathological RoIs on the 10 x 30 level
     scales = [1 / 8, 1 / 16, 1 / 32, 1 / 4]
@@ -832,7 +803,7 @@ def test_roi_align_standalone_quad_kernel_vs_oracle(dev, C):
     grids = [(19, 32), (10, 30)]
     feats = inputs.feature_maps(70, grids, C, 2)
     wide = np.array([[1, 0, 0, 119, 39], [0, 2, 1, 110, 38], [1, 30, 20, 1000, 500]], np.float32)
-    rois = np.concatenate([_rois(71, 40, 2), wide[2:], _pathological_rois(2), wide[:2]], 0)
+    rois = np.concatenate([support.rois(71, 40, 2), wide[2:], support.pathological_rois(2), wide[:2]], 0)
     levels = np.zeros(len(rois), np.int64)
     levels[-13:] = 1  # the pathological and the first two wide RoIs on the 10 x 30 level
     scales = [1 / 32, 1 / 4]
@@ -846,7 +817,7 @@ def test_roi_align_module_and_strided_view(dev):
     from frcnn_amd.ops import RoIAlign
     f = inputs.feature_maps(50, [(40, 60)], 32, 2)[0]
     ft = T(f, dev)[:, :, ::2, ::2]  # non-contiguous (FPN P6 style)
-    rois = _rois(51, 200, 2)
+    rois = support.rois(51, 200, 2)
     out = RoIAlign((7, 7), 0.25, 2)(ft, T(rois, dev)).cpu().numpy()
     ref = oracle.roi_align([np.ascontiguousarray(f[:, :, ::2, ::2])], rois, None, [0.25], (7, 7), 2)
     np.testing.assert_array_equal(out, ref)
@@ -867,7 +838,7 @@ def test_roi_align_backward_vs_oracle(dev, case):
     sr = 0 if case == 'adaptive' else 2
     ph, pw = (9, 7) if case == 'bins9x7' else (7, 7)
     feats = inputs.feature_maps(60, grids, C, 2)
-    rois = _rois(61, K, 2)
+    rois = support.rois(61, K, 2)
     levels = oracle.roi_level_map(rois, 56.0, L)
     g = np.random.default_rng(62).standard_normal((K, C, ph, pw)).astype(np.float32)
     ft = [T(f, dev) for f in feats]
@@ -900,7 +871,7 @@ def test_roi_align_backward_deterministic(dev, case, gscale):
         grids, scales, C = [tuple(int(v) for v in s[2:]) for s in z['shapes']], [float(v) for v in z['scales']], 64
     else:
         grids, scales, C = [(152, 256), (76, 128)], [1 / 4, 1 / 8], 80
-        rois = _rois(61, 300, 2)
+        rois = support.rois(61, 300, 2)
         levels = oracle.roi_level_map(rois, 56.0, 2)
     K = rois.shape[0]
     feats = inputs.feature_maps(60, grids, C, 2)
@@ -934,7 +905,7 @@ def test_roi_align_backward_deterministic_nonfinite_and_unsupported(dev):
     from frcnn_amd import ops
     grids, scales, C = [(38, 64)], [1 / 16], 16
     feats = inputs.feature_maps(64, grids, C, 2)
-    rois = _rois(65, 40, 2)
+    rois = support.rois(65, 40, 2)
     g = np.random.default_rng(66).standard_normal((40, C, 7, 7)).astype(np.float32)
     g[3, 2, 1, 1] = np.nan
     ops.set_deterministic_backward(True)
@@ -953,7 +924,7 @@ def test_roi_align_backward_deterministic_nonfinite_and_unsupported(dev):
 def test_roi_pool_vs_oracle(dev):
     from frcnn_amd.ops import RoIPool
     f = inputs.feature_maps(70, [(38, 64)], 32, 2)[0]
-    rois = _rois(71, 150, 2)
+    rois = support.rois(71, 150, 2)
     out = RoIPool((7, 7), 1 / 16, sampling_ratio=2)(T(f, dev), T(rois, dev)).cpu().numpy()
     ref, _ = oracle.roi_pool(f, rois, (7, 7), 1 / 16)
     np.testing.assert_array_equal(out, ref)

@@ -12,22 +12,15 @@ Runs in a spawned process so the test process never holds an RCCL communicator."
 import copy
 import hashlib
 import os
-import socket
 
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 STEPS = 2
-
-
-def _port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(port, q):
@@ -81,7 +74,7 @@ def test_world1_nccl_ddp_train_step_equals_plain_step(dev):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    p = ctx.Process(target=_worker, args=(_port(), q))
+    p = ctx.Process(target=_worker, args=(support.free_port(), q))
     p.start()
     try:
         res = q.get(timeout=400)

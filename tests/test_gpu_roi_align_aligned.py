@@ -23,30 +23,11 @@ import torch
 
 import inputs
 import oracle
+import support
 
 GRIDS = [(19, 32), (10, 30)]
 SCALES = [1 / 32, 1 / 4]
 B = 2
-
-
-def _rois(seed, n, batch):
-    b = inputs.random_boxes(seed, n, min_wh=1.0, max_wh=500.0)
-    b[:, :8] = np.array([[-20, -20, 10, 10], [990, 590, 1200, 700], [0, 0, 0, 0], [5, 5, 5.5, 5.2],
-                         [998.9, 598.9, 999, 599], [-300, -300, -200, -100], [0, 0, 999, 599],
-                         [100.25, 200.75, 101.0, 260.5]], np.float32).T
-    bi = np.random.default_rng(seed + 1).integers(0, batch, n).astype(np.float32)
-    return np.concatenate([bi[None], b], 0).T.copy()
-
-
-def _pathological_rois(batch):
-    """RoIs whose dense tap windows defeat row bands: far larger than a 10 x 30 level, so one bin
-    row's two samples lie 3.6 rows apart with every row between them inside the window, plus RoIs
-    hanging off every edge, tiny and degenerate ones."""
-    r = np.array([[0, 0, 0, 400, 200], [1, -50, -40, 380, 230], [0, 3, 2, 900, 60], [1, 100, 0, 119.5, 300],
-                  [0, -500, -500, 600, 600], [1, 0, 30, 119, 36], [0, 60, 10, 61, 11], [1, 119, 39, 119, 39],
-                  [0, -30, -30, -1, -1], [1, 10, -10, 110, 45], [0, 0, 0, 1000, 200]], np.float32)
-    r[:, 0] %= batch
-    return r
 
 
 @functools.lru_cache(maxsize=None)
@@ -55,7 +36,7 @@ def _set():
     wide = np.array([[1, 0, 0, 119, 39], [0, 2, 1, 110, 38], [1, 30, 20, 1000, 500]], np.float32)
     # whole-map RoIs on the 19 x 32 level: windows of 19 rows x 28 tap-list columns (> 480 cells)
     large = np.array([[0, -10, -10, 1100, 650], [1, 0, 0, 1023, 607], [0, 5, 3, 1015, 600]], np.float32)
-    rois = np.concatenate([large, _rois(61, 64, B), wide[2:], _pathological_rois(B), wide[:2]], 0)
+    rois = np.concatenate([large, support.rois(61, 64, B), wide[2:], support.pathological_rois(B), wide[:2]], 0)
     levels = np.zeros(len(rois), np.int64)
     levels[-13:] = 1  # the pathological and the first two wide RoIs on the 10 x 30 level
     assert np.all(rois[:, 3] >= rois[:, 1]) and np.all(rois[:, 4] >= rois[:, 2])
@@ -239,7 +220,7 @@ def test_module_on_a_strided_view(dev):
     f = inputs.feature_maps(92, [(40, 60)], 32, B)[0]
     ft = torch.from_numpy(f).to(dev)[:, :, ::2, ::2]
     assert not ft.is_contiguous()
-    rois = _rois(93, 64, B)
+    rois = support.rois(93, 64, B)
     out = RoIAlign((7, 7), 1 / 32, 2, aligned=True)(ft, torch.from_numpy(rois).to(dev)).cpu().numpy()
     ref = oracle.roi_align([np.ascontiguousarray(f[:, :, ::2, ::2])], rois, None, [1 / 32], (7, 7), 2, aligned=True)
     np.testing.assert_array_equal(out, ref)

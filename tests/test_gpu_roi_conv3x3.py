@@ -17,6 +17,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [
@@ -200,9 +202,7 @@ def test_dispatch(dev, monkeypatch):
     """An eval head under no_grad takes the fused entry; a training BN, a gradient needed, stride 2
     and a biased conv take relu(bn(conv(x))) with no library call, and give PyTorch's result."""
     from frcnn_amd import ops
-    names = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    spy = support.spy_entries(monkeypatch)
     x = torch.randn(9, 32, 7, 7, device=dev)
 
     conv, bn = _conv_bn(dev, 32, 64)
@@ -210,20 +210,20 @@ def test_dispatch(dev, monkeypatch):
     with torch.no_grad():
         assert ops.roi_conv3x3_fused_ok(conv, bn, x)
         got = ops.roi_conv3x3_bn_act(conv, bn, x)
-        assert names == ['frh_roi_conv3x3_bn_act']
+        assert spy.names == ['frh_roi_conv3x3_bn_act']
         want = torch.relu(bn(conv(x)))
         # MIOpen's own sum order differs: close, not equal
         assert torch.allclose(got, want, rtol=1e-4, atol=1e-4)
 
     def falls_back(conv, bn, xi, grad):
-        del names[:]
+        spy.clear()
         ctx = torch.enable_grad() if grad else torch.no_grad()
         with ctx:
             assert not ops.roi_conv3x3_fused_ok(conv, bn, xi)
             torch.relu(bn(conv(xi)))  # MIOpen settles on its solver for this shape
             got = ops.roi_conv3x3_bn_act(conv, bn, xi)
             want = torch.relu(bn(conv(xi)))
-        assert names == []
+        assert spy.names == []
         assert torch.equal(got, want)
         return got
 

@@ -29,19 +29,11 @@ import torch
 
 import inputs
 import oracle
+import support
 
 H, W, C, B = 38, 64, 8, 2
 PH, PW = 7, 7
 SCALE = 1.0 / 16.0
-
-
-def _rois(seed, n, batch):
-    b = inputs.random_boxes(seed, n, min_wh=1.0, max_wh=500.0)
-    b[:, :8] = np.array([[-20, -20, 10, 10], [990, 590, 1200, 700], [0, 0, 0, 0], [5, 5, 5.5, 5.2],
-                         [998.9, 598.9, 999, 599], [-300, -300, -200, -100], [0, 0, 999, 599],
-                         [100.25, 200.75, 101.0, 260.5]], np.float32).T
-    bi = np.random.default_rng(seed + 1).integers(0, batch, n).astype(np.float32)
-    return np.concatenate([bi[None], b], 0).T.copy()
 
 
 @functools.lru_cache(maxsize=None)
@@ -49,7 +41,7 @@ def _case():
     """The inputs and the oracle's results, computed once and shared (treated as read-only)."""
     f = inputs.feature_maps(70, [(H, W)], C, B)[0]
     fq = (np.round(np.maximum(f, 0) * 2) / 2).astype(np.float32)
-    rois = _rois(71, 64, B)
+    rois = support.rois(71, 64, B)
     assert np.all(rois[:, 3] >= rois[:, 1]) and np.all(rois[:, 4] >= rois[:, 2])
     d = dict(rois=rois, cont=f, quant=fq)
     for name in ('cont', 'quant'):

@@ -11,6 +11,8 @@ import functools
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 CASES = [
@@ -163,9 +165,7 @@ def test_dispatch_with_gradients(dev, monkeypatch):
     case = CASES[1]
     d = _on_dev(case, 'randn', dev)
     classifier, regressor = _modules(dev, case, d)
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     with torch.enable_grad():
         for x in d['xs']:  # MIOpen's first call of a shape may take another solver than the later ones
             classifier(x), regressor(x)
@@ -184,9 +184,7 @@ def test_dispatch_under_no_grad(dev, case, monkeypatch):
     from frcnn_amd import ops
     d = _on_dev(case, 'randn', dev)
     classifier, regressor = _modules(dev, case, d)
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     with torch.no_grad():
         cls, reg = ops.rpn_head1x1_levels(classifier, regressor, d['xs'])
         assert names == ['frh_rpn_head1x1_levels']
@@ -198,7 +196,6 @@ def test_dispatch_under_no_grad(dev, case, monkeypatch):
 
 def test_rpn_head_forward_takes_it(dev, monkeypatch):
     """RPNHead.forward under no_grad: its two 1x1 convs are the one launch."""
-    from frcnn_amd import ops
     from frcnn_amd.heads.rpn_head import RPNHead
     torch.manual_seed(2)
     head = RPNHead(64, 64, loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True),
@@ -206,9 +203,7 @@ def test_rpn_head_forward_takes_it(dev, monkeypatch):
     head = head.to(memory_format=torch.channels_last)
     xs = [torch.randn(2, 64, h, w, device=dev).contiguous(memory_format=torch.channels_last)
           for h, w in ((6, 8), (3, 4))]
-    names = []
-    real_call = ops.call
-    monkeypatch.setattr(ops, 'call', lambda name, *a: (names.append(name), real_call(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     with torch.no_grad():
         cls, reg = head(xs)
         assert names.count('frh_rpn_head1x1_levels') == 1

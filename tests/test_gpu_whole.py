@@ -14,51 +14,23 @@ refine, multiclass NMS and the fused losses.  Bars: losses rel 2e-5 (the fused l
 in double, torch CPU in float), detections in the reference's order with labels exact,
 scores rel 1e-6 and boxes within a few f32 ulps (rel 2e-6: the decode's expf / the
 ATSS ltrb scale round differently from torch's CPU vector math in the last bit)."""
-import copy
 import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import inputs
+import support
 
 pytestmark = pytest.mark.gpu
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {c[0]: c for c in inputs.WHOLE_DETECTORS}
 
 
 def _model(fname, over):
-    from frcnn_amd.config import Config
-    from frcnn_amd.builder import build_module
-    cfg = Config.fromfile(os.path.join(REPO, 'pytorch-faster-rcnn_amd', 'configs', fname))
-    for k, v in over.items():
-        cfg.test_cfg[k].update(v)
-    model = build_module(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-    sd = inputs.seeded_state({k: tuple(v.shape) for k, v in model.state_dict().items()})
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model = support.load_seeded(support.build_whole(fname, over))
     model.train()
     return model
-
-
-def _to(x, dev):
-    if torch.is_tensor(x):
-        return x.to(dev)
-    if isinstance(x, (list, tuple)):
-        return type(x)(_to(v, dev) for v in x)
-    return x
-
-
-def _on_cpu(module, dev):
-    """Run `module` (a PyTorch conv / FC stack) on a CPU copy of itself, outputs back on dev."""
-    cpu = copy.deepcopy(module).cpu()
-
-    def forward(*args):
-        with torch.no_grad():
-            return _to(cpu(*[_to(a, 'cpu') for a in args]), dev)
-    module.forward = forward
 
 
 def _prepare(tag, dev):
@@ -72,17 +44,16 @@ def _prepare(tag, dev):
     dfeats = [f.to(dev) for f in feats]
     model.extract_feat = lambda img_data: dfeats
     if hasattr(model, 'rpn_head'):
-        _on_cpu(model.rpn_head, dev)
+        support.on_cpu(model.rpn_head, dev, pinned=False)
         for h in model.rcnn_head:  # the FC stack only: RoI features come from the HIP RoIAlign
             for name in ('shared_fcs', 'classifier', 'regressor'):
                 if getattr(h, name, None) is not None:
-                    _on_cpu(getattr(h, name), dev)
+                    support.on_cpu(getattr(h, name), dev, pinned=False)
     else:
-        _on_cpu(model.bbox_head, dev)
+        support.on_cpu(model.bbox_head, dev, pinned=False)
     from frcnn_amd import set_sampler_mode
     set_sampler_mode('numpy')
-    return model, x.to(dev), [torch.from_numpy(b).to(dev) for b in boxes], \
-        [torch.from_numpy(l).to(dev) for l in labels], metas
+    return (model, x.to(dev)) + support.gts_on(dev, boxes, labels) + (metas,)
 
 
 @pytest.mark.parametrize('tag', sorted(CASES))
@@ -90,22 +61,11 @@ def test_whole_forward_train_losses_vs_reference(dev, tag):
     ref = json.load(open(inputs.golden_path('whole_{}.json'.format(tag))))
     model, x, boxes, labels, metas = _prepare(tag, dev)
     if hasattr(model, 'graphed_trunk'):  # CascadeRCNN's trunk hook: feats + RPN outputs of the CPU trunk
-        feats = model.extract_feat(x)
-        rpn = model.rpn_head(feats)
-
-        class CpuTrunk(object):
-            def matches(self, img_data):
-                return True
-
-            def __call__(self, img_data):
-                return feats, rpn[0], rpn[1]
-        model.graphed_trunk = CpuTrunk()
+        support.use_cpu_trunk(model, x)
     np.random.seed(inputs.FTRAIN_NP_SEED)
     with torch.no_grad():
         losses = model.forward_train(x, boxes, labels, metas)
-    assert set(losses) == set(ref['losses'])
-    for k, v in ref['losses'].items():
-        assert float(losses[k]) == pytest.approx(v, rel=2e-5), (k, float(losses[k]), v)
+    support.assert_losses_match(losses, ref['losses'], rel=2e-5)
 
 
 @pytest.mark.parametrize('tag', sorted(CASES))
@@ -115,16 +75,8 @@ def test_whole_forward_test_detections_vs_reference(dev, tag):
     model.eval()
     with torch.no_grad():
         dets = model.forward_test(x, metas)
-    boxes, scores, labels = dets[:3]
-    assert len(boxes) == int(z['n'])
-    for i in range(int(z['n'])):
-        rb, rs, rl = z['boxes_{}'.format(i)], z['scores_{}'.format(i)], z['labels_{}'.format(i)]
-        gb = boxes[i].t().cpu().numpy()
-        gs, gl = scores[i].cpu().numpy(), labels[i].cpu().numpy()
-        assert len(rs) > 0 and gs.shape == rs.shape, (gs.shape, rs.shape)
-        np.testing.assert_array_equal(gl, rl)
-        np.testing.assert_allclose(gs, rs, rtol=1e-6, atol=0)
-        np.testing.assert_allclose(gb, rb, rtol=2e-6, atol=1e-4)  # a few f32 ulps (exp / ltrb decode)
+    # boxes: a few f32 ulps (exp / ltrb decode)
+    support.assert_detections_match(dets, z, score_rtol=1e-6, box_rtol=2e-6, box_atol=1e-4)
 
 
 def test_device_sampler_targets_and_losses_vs_oracle(dev):
@@ -139,7 +91,6 @@ def test_device_sampler_targets_and_losses_vs_oracle(dev):
     the encoded params within 1 ulp (logf); losses rel 2e-5 (as the whole-detector tests)."""
     import pipeline
     from frcnn_amd import ops, set_sampler_mode
-    from frcnn_amd.config import Config
     _, fname, over, shape = CASES['cfg2']
     model, x, boxes, labels, metas = _prepare('cfg2', dev)
     cap = {'sample': [], 'anchor_target': [], 'bbox_target': []}
@@ -197,9 +148,7 @@ def test_device_sampler_targets_and_losses_vs_oracle(dev):
         hook.sampled[stage] = out
         return out
     hook.sampled = {}
-    cfg = Config.fromfile(os.path.join(REPO, 'pytorch-faster-rcnn_amd', 'configs', fname))
-    for k, v in over.items():
-        cfg.test_cfg[k].update(v)
+    cfg = support.whole_config(fname, over)
     cpu_model = _model(fname, over)
     head = cpu_model.rpn_head
     with torch.no_grad():
@@ -210,9 +159,7 @@ def test_device_sampler_targets_and_losses_vs_oracle(dev):
     with torch.no_grad():
         ref = pipeline.forward_train_cpu(cpu_model, cfg, x.cpu(), [b.cpu() for b in boxes],
                                          [l.cpu() for l in labels], metas, sampler_hook=hook)
-    assert set(ref) == set(losses)
-    for k in ref:
-        assert float(losses[k]) == pytest.approx(float(ref[k]), rel=2e-5), (k, float(losses[k]), float(ref[k]))
+    support.assert_losses_match(losses, ref, rel=2e-5)
     # the RPN targets, column by column (image 0 = the first device segment)
     at = cap['anchor_target'][0]
     a = cfg.train_cfg.rpn.assigner

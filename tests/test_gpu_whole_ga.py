@@ -16,10 +16,8 @@ so the proposals are compared in order.
 
 Plus the eval model wholly on the device: the adaption layer of all five levels is ONE
 frh_deform_conv3x3_act_levels call, and its detections are finite."""
-import contextlib
 import copy
 import json
-import os
 
 import numpy as np
 import pytest
@@ -27,55 +25,13 @@ import torch
 
 import ga_inputs
 import inputs
+import support
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE_THREADS = 8
-
 
 def _build():
-    from frcnn_amd.config import Config
-    from frcnn_amd.builder import build_module
-    cfg = Config.fromfile(os.path.join(REPO, 'pytorch-faster-rcnn_amd', 'configs', ga_inputs.WHOLE_CONFIG))
-    for k, v in ga_inputs.WHOLE_TEST_OVERRIDES.items():
-        cfg.test_cfg[k].update(v)
-    return build_module(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-
-
-def _to(x, dev):
-    if torch.is_tensor(x):
-        return x.to(dev)
-    if isinstance(x, (list, tuple)):
-        return type(x)(_to(v, dev) for v in x)
-    return x
-
-
-def _nchw(x):
-    if torch.is_tensor(x):
-        return x.contiguous()
-    return type(x)(_nchw(v) for v in x) if isinstance(x, (list, tuple)) else x
-
-
-@contextlib.contextmanager
-def _fixture_threads():
-    """PyTorch's CPU convolutions round differently with the thread count: the CPU layers run
-    with the generator's (gen_ga_golden.main: 8)."""
-    n = torch.get_num_threads()
-    torch.set_num_threads(FIXTURE_THREADS)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(n)
-
-
-def _on_cpu(module, dev):
-    cpu = copy.deepcopy(module).cpu()
-
-    def forward(*args):
-        with torch.no_grad(), _fixture_threads():
-            return _to(cpu(*[_nchw(_to(a, 'cpu')) for a in args]), dev)
-    module.forward = forward
+    return support.build_whole(ga_inputs.WHOLE_CONFIG, ga_inputs.WHOLE_TEST_OVERRIDES)
 
 
 def _rcnn_on_cpu(head, dev):
@@ -86,7 +42,7 @@ def _rcnn_on_cpu(head, dev):
         flat = getattr(rois, 'flat', None)
         x = flat if flat is not None else torch.cat(list(rois), 0)
         sizes = [r.shape[0] for r in rois]
-        with torch.no_grad(), _fixture_threads():
+        with torch.no_grad(), support.fixture_threads():
             cls_out, reg_out = cpu([x.cpu().contiguous()])[0].flat
         cls_out, reg_out = cls_out.to(dev), reg_out.to(dev)
         cls_outs, reg_outs = HeadOutputs(), HeadOutputs()
@@ -101,10 +57,7 @@ def _rcnn_on_cpu(head, dev):
 
 
 def _seeded():
-    model = _build()
-    sd = ga_inputs.whole_state({k: tuple(v.shape) for k, v in model.state_dict().items()})
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    return model
+    return support.load_seeded(_build(), state=ga_inputs.whole_state)
 
 
 def _prepare(dev, training):
@@ -113,16 +66,15 @@ def _prepare(dev, training):
     model.train(training)
     img, boxes, labels, metas = inputs.ftrain_case(ga_inputs.WHOLE_SHAPE)
     x = torch.from_numpy(img)
-    with torch.no_grad(), _fixture_threads():
+    with torch.no_grad(), support.fixture_threads():
         feats = [f.to(dev) for f in model.neck(model.backbone(x))]  # CPU convs, as in the fixture
     model = model.to(dev)
     model.extract_feat = lambda img_data: feats
-    _on_cpu(model.rpn_head, dev)
+    support.on_cpu(model.rpn_head, dev)
     for h in model.rcnn_head:
         _rcnn_on_cpu(h, dev)
     set_sampler_mode('numpy')
-    return model, x.to(dev), [torch.from_numpy(b).to(dev) for b in boxes], \
-        [torch.from_numpy(l).to(dev) for l in labels], metas
+    return (model, x.to(dev)) + support.gts_on(dev, boxes, labels) + (metas,)
 
 
 def test_config_builds_with_the_reference_keys():
@@ -138,11 +90,7 @@ def test_ga_forward_train_losses_vs_reference(dev):
     np.random.seed(inputs.FTRAIN_NP_SEED)
     with torch.no_grad():
         losses = model.forward_train(x, boxes, labels, metas)
-    assert set(losses) == set(ref['losses'])
-    for k, v in ref['losses'].items():
-        print(k, float(losses[k]), v)
-    for k, v in ref['losses'].items():
-        assert float(losses[k]) == pytest.approx(v, rel=2e-5), (k, float(losses[k]), v)
+    support.assert_losses_match(losses, ref['losses'], rel=2e-5)
 
 
 def test_ga_forward_test_detections_vs_reference(dev):
@@ -154,25 +102,13 @@ def test_ga_forward_test_detections_vs_reference(dev):
     # the proposals, scores and boxes, in order
     np.testing.assert_allclose(props[1][0].cpu().numpy(), z['prop_scores_0'], rtol=1e-6, atol=0)
     np.testing.assert_allclose(props[0][0].cpu().numpy(), z['props_0'], rtol=2e-6, atol=1e-4)
-    boxes, scores, labels = dets[:3]
-    assert len(boxes) == int(z['n'])
-    for i in range(int(z['n'])):
-        rb, rs, rl = z['boxes_{}'.format(i)], z['scores_{}'.format(i)], z['labels_{}'.format(i)]
-        gb = boxes[i].t().cpu().numpy()
-        gs, gl = scores[i].cpu().numpy(), labels[i].cpu().numpy()
-        assert len(rs) > 0 and gs.shape == rs.shape, (gs.shape, rs.shape)
-        np.testing.assert_array_equal(gl, rl)
-        np.testing.assert_allclose(gs, rs, rtol=1e-6, atol=0)
-        np.testing.assert_allclose(gb, rb, rtol=2e-6, atol=1e-4)
+    support.assert_detections_match(dets, z, score_rtol=1e-6, box_rtol=2e-6, box_atol=1e-4)
 
 
 def test_eval_forward_on_the_device_launches_the_levels_entry_once(dev, monkeypatch):
-    from frcnn_amd import ops
     model = _seeded().to(dev).eval()
     img, _, _, metas = inputs.ftrain_case(ga_inputs.WHOLE_SHAPE)
-    names = []
-    real = ops._call
-    monkeypatch.setattr(ops, '_call', lambda name, *a: (names.append(name), real(name, *a))[1])
+    names = support.spy_entries(monkeypatch).names
     with torch.no_grad():
         dets = model.forward_test(torch.from_numpy(img).to(dev), metas)
     assert names.count('frh_deform_conv3x3_act_levels') == 1 and 'frh_deform_conv3x3_act' not in names

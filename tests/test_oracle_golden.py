@@ -1,17 +1,12 @@
 """Pin the CPU oracle against golden vectors produced by the reference itself
 (tests/golden/gen_golden.py).  CPU only; these are what make the oracle a
 trustworthy checker for the GPU parity tests."""
-import hashlib
-
 import numpy as np
 import pytest
 
 import inputs
 import oracle
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+from support import canon_ties, sha
 
 
 def fpn_anchors(strides=inputs.FPN_STRIDES, grids=inputs.FPN_GRIDS, scales=(8,), ratios=(0.5, 1.0, 2.0)):
@@ -23,12 +18,6 @@ def fpn_in_mask(anchors):
     ingrid = np.concatenate([oracle.inside_grid_mask(3, inputs.IMG_SHAPE, g, s)
                              for g, s in zip(inputs.FPN_GRIDS, inputs.FPN_STRIDES)]).astype(bool)
     return ingrid & oracle.inside_anchor_mask(anchors, inputs.IMG_SHAPE, 0)
-
-
-def canon_ties(boxes, scores):
-    """Reorder columns so that runs of equal scores are sorted by coordinates."""
-    order = np.lexsort((boxes[3], boxes[2], boxes[1], boxes[0], -scores.astype(np.float64)))
-    return boxes[:, order]
 
 
 CASES = {

@@ -5,12 +5,13 @@ img_metas) -> loss dict; after one step both ranks must hold identical parameter
 one clipped SGD step on the rank-averaged gradient (the reference's
 lib/trainer/trainer.py:100-127 + hooks.py:55-59 semantics with DDP averaging)."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 from torch import nn
+
+import support
 
 OPT = dict(type='SGD', lr=0.1, momentum=0.9, weight_decay=1e-4)
 CLIP = dict(max_norm=0.5, norm_type=2)
@@ -37,14 +38,6 @@ def _batch(rank):
     g = torch.Generator().manual_seed(100 + rank)
     return (torch.randn(3, 2, 3, generator=g), torch.randn(3, 4, generator=g),
             torch.randint(0, 5, (3,), generator=g), [{}] * 3)
-
-
-def _port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -78,7 +71,7 @@ def _expected(world):
 def test_two_rank_ddp_step_matches_averaged_gradient_step():
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    port = _port()
+    port = support.free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
