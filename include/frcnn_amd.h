@@ -787,7 +787,10 @@ int32_t frh_bias_act_nhwc(float* y, const float* bias, int64_t rows, int32_t cha
  * reductions): kind 0 = sigmoid_focal_loss (losses.py:33-61, one-hot[:, 1:] targets),
  * 1 = CrossEntropyLoss(use_sigmoid=True) (losses.py:139-150; C == 1 takes the target
  * value itself, int64 or, with target_is_float, f32), 2 = CrossEntropyLoss softmax
- * (losses.py:151-153, labels in [0, C)).  Logit (i, k) is x[i*sr + k*sc] (any strides,
+ * (losses.py:151-153, labels in [0, C)).  alpha / gamma are read by kind 0 only; the supported
+ * focal gamma is 0 or >= 1 (for 0 < gamma < 1 the derivative gamma * q^(gamma-1) is infinite
+ * where the logit saturates, q = 1 - pt == 0, in torch as here; gamma == 0 drops that term,
+ * as torch's pow backward does).  Logit (i, k) is x[i*sr + k*sc] (any strides,
  * so AnchorHead's [C, S] targets need no transpose copy); out is one f32 on the device.
  * status (nullable, ABI 3): the device status word; while it is nonzero the forward writes NaN.
  * Backward writes grad_x (i, k) at grad_x[i*gsr + k*gsc] = grad_out[0] * dL/dx.  Rows with an

@@ -47,8 +47,9 @@ __device__ __forceinline__ float focal_elem(float x, float t, float alpha, float
   float bce = bce_logits(x, t);
   if (dx) {
     // d/dx [bce * at * q^gamma] = (p - t) * w + bce * at * gamma * q^(gamma-1) * (-dpt/dx),
-    // dpt/dx = p (1 - p) (2t - 1)
-    float dq = gamma * powf(q, gamma - 1.0f);
+    // dpt/dx = p (1 - p) (2t - 1).  gamma == 0: q^0 is the constant 1 and the term is 0, as torch's
+    // pow backward has it; gamma * q^(gamma-1) would be 0 * inf = NaN where q == 0 (|x| >= 17)
+    float dq = gamma == 0.0f ? 0.0f : gamma * powf(q, gamma - 1.0f);
     float dpt = p * (1.0f - p) * (2.0f * t - 1.0f);
     *dx = (p - t) * w - bce * at * dq * dpt;
   }
