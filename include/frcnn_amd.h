@@ -650,6 +650,36 @@ int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, c
                                     const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
                                     void* stream);
 
+/* The prediction convs of a one-stage head (lib/heads/retina_head.py:87, RetinaHead.forward:
+ * retina_cls / retina_reg; lib/heads/fcos_head.py:266-281, FCOSHead.forward: fcos_cls / fcos_reg /
+ * fcos_center): 3x3, stride 1, padding 1, no groups, no dilation, over every level of the pyramid
+ * in one launch, with no weight-transform launch and no workspace.  One conv (c1 == 0, w1 NULL)
+ * or two that read the same input, each level read once for both.
+ * Inputs: num_levels (1..8) levels xs[i] f32 [n, level_hw[2i], level_hw[2i + 1], cin] with channel
+ * stride 1 and element strides level_strides[3i..] = (image, row, column; non-negative multiples
+ * of 4, so a [:, :, ::2, ::2] view runs without a copy).  Weights: w0 [c0][3][3][cin] and w1
+ * [c1][3][3][cin], the channels-last Conv2d weight as it lies in memory; b0 / b1 [c0] / [c1] or
+ * NULL.  Outputs: ys0[i] [n, h_i, w_i, c0] and ys1[i] [n, h_i, w_i, c1], contiguous channels-last
+ * (ys1 is not read when c1 == 0).  cin % 8 == 0, c0 >= 1, c0 + c1 <= 192, inputs and weights
+ * 16-byte aligned, no output sharing a byte with an input or a weight (anything else:
+ * FRH_EINVAL and no launch); a level with n, h or w zero launches nothing.
+ * Epilogue of conv k, in this order, each statement rounded once (no contraction):
+ * v = acc + bias; v = v * scales_k[i][c] where scales_k (an array of num_levels device pointers
+ * to [c_k] floats) and its entry i are not NULL; v = expf(v) where exp_k != 0.  That is plain
+ * logits, FCOS's exp(conv(x) * reg_coef[i]), and DFL's conv(x) * coef with
+ * coef[bin * 4 + side] = reg_coef[i][bin].
+ * A direct convolution on the exact-f32 MFMA (16x16x4), not Winograd: every output element is
+ * one fmaf chain over its 9 * cin products in one fixed order (16-channel group, then tap, then
+ * channel within the group), with no atomics and no split over cin.  The bits of an output
+ * element depend on its inputs only: not on the level, the pixel's place in a tile, the other
+ * conv or the other levels of the launch, nor on the launch.  Asynchronous on stream: no
+ * synchronisation, allocation or global state (capturable into a hipGraph). */
+int32_t frh_conv3x3_out_levels(int32_t num_levels, const void* const* xs, void* const* ys0, void* const* ys1,
+                               const float* w0, const float* b0, const float* w1, const float* b1,
+                               const void* const* scales0, const void* const* scales1, int32_t exp0, int32_t exp1,
+                               int64_t n, int32_t cin, int32_t c0, int32_t c1, const int32_t* level_hw,
+                               const int64_t* level_strides, void* stream);
+
 /* A bottleneck's 3x3 / stride-1 / padding-1 convolution (torchvision Bottleneck.forward: conv2,
  * followed by its frozen BN and ReLU) as Winograd F(2x2, 3x3) on the f32 MFMA with the
  * frh_bn_act epilogue on the accumulators: y[n, co] = act(conv3x3(x[n], w[co]) * s[co] + b[co]),

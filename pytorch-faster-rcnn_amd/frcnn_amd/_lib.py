@@ -114,6 +114,8 @@ SIGNATURES = {
                                      c_i32, c_vp]),
     'frh_conv3x3_bias_act_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), P(c_vp), P(c_vp), c_vp, c_size, c_i64, c_i32, c_i32,
                                             P(c_i32), P(c_i64), c_i32, c_vp]),
+    'frh_conv3x3_out_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), P(c_vp), c_vp, c_vp, c_vp, c_vp, P(c_vp), P(c_vp),
+                                       c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, P(c_i32), P(c_i64), c_vp]),
     'frh_conv3x3_nchw_workspace': (c_size, [c_i32, c_i32]),
     'frh_conv3x3_nchw_bn_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
                                         c_i32, c_i32, c_vp]),

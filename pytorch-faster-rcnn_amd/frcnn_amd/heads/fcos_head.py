@@ -10,6 +10,10 @@ decodes its boxes with `ops.dfl_decode` (frh_dfl_decode, :579-600); the head wit
 `ops.fcos_losses` launch (frh_fcos_loss_fwd / _bwd).  Inference (:566-627) builds the NMS
 input of the whole batch with one `ops.dense_candidates` call (frh_dense_candidates) and runs
 one batched multiclass NMS; the GFL head keeps its per-level decode until `dense_dfl` is set.
+`forward` (:266-281) at inference runs its towers on `ops.head_tower_levels`
+(frh_conv3x3_bias_act_levels) and its output convs on `ops.conv3x3_out_levels`
+(frh_conv3x3_out_levels); with a gradient needed, on CPU tensors and for narrow heads it is the
+module expressions.
 The other loss combinations (QFL alone, DFL alone) and CPU tensors (image_candidates, also
 the tests' oracle) are PyTorch-ROCm tensor code around them.
 The LTRB helpers keep the reference's names and semantics.
@@ -191,6 +195,10 @@ class FCOSHead(ChannelsLastConvs):
         _normal_init(self.fcos_center, 0.01)
 
     def forward(self, xs):
+        xs = list(xs)
+        if ops.head_convs_fused_ok([self.cls_convs, self.reg_convs], [[self.fcos_cls], [self.fcos_reg, self.fcos_center]],
+                                   xs, extra=(self.reg_coef,)):
+            return self._forward_fused(xs)
         cls_t = [self.cls_convs(x) for x in xs]
         reg_t = [self.reg_convs(x) for x in xs]
         cls_outs = [self.fcos_cls(x) for x in cls_t]
@@ -202,6 +210,25 @@ class FCOSHead(ChannelsLastConvs):
                 reg_outs.append(self.fcos_reg(x) * coef.view(-1, 1, 1))
         else:
             reg_outs = [torch.exp(self.fcos_reg(x) * self.reg_coef[i]) for i, x in enumerate(reg_t)]
+        return cls_outs, reg_outs, ctr_outs
+
+    def _forward_fused(self, xs):
+        """forward (fcos_head.py:266-281) at inference on channels-last HIP levels: each tower layer
+        one Winograd launch pair over the levels, fcos_cls one direct-convolution launch, fcos_reg
+        and fcos_center one launch that reads the regression tower once, with the reg_coef multiply
+        (and the exp without DFL) on the accumulators."""
+        coef = self.reg_coef.detach()
+        if len(xs) > coef.shape[0]:
+            raise IndexError('more levels than reg_coef entries')
+        if self.use_dfl:  # channel bin * 4 + side takes reg_coef[level][bin]
+            scale = coef.unsqueeze(2).expand(-1, -1, 4).reshape(coef.shape[0], -1)
+        else:
+            scale = coef.view(-1, 1).expand(-1, 4).contiguous()
+        (cls_outs,) = ops.conv3x3_out_levels([self.fcos_cls], ops.head_tower_levels(self.cls_convs, xs))
+        reg_outs, ctr_outs = ops.conv3x3_out_levels([self.fcos_reg, self.fcos_center],
+                                                    ops.head_tower_levels(self.reg_convs, xs),
+                                                    scales=[[scale[i] for i in range(len(xs))], None],
+                                                    exp=[not self.use_dfl, False])
         return cls_outs, reg_outs, ctr_outs
 
     # ------------------------------------------------------------ ATSS targets (HIP)

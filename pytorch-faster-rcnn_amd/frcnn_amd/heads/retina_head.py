@@ -1,8 +1,10 @@
 """RetinaHead (reference lib/heads/retina_head.py): 9 octave anchors per location,
-stacked conv towers (PyTorch-ROCm); targets/NMS through AnchorHead's HIP path."""
+stacked conv towers (at inference the fused HIP convolutions, ops.head_tower_levels and
+ops.conv3x3_out_levels; PyTorch-ROCm in training); targets/NMS through AnchorHead's HIP path."""
 import numpy as np
 from torch import nn
 
+from .. import ops
 from .anchor_head import AnchorHead
 
 
@@ -48,6 +50,13 @@ class RetinaHead(AnchorHead):
         _normal_init(self.retina_reg, 0.01)
 
     def forward(self, xs):
+        xs = list(xs)
+        if ops.head_convs_fused_ok([self.cls_convs, self.reg_convs], [[self.retina_cls], [self.retina_reg]], xs):
+            # inference on channels-last HIP levels: each tower layer one Winograd launch pair over
+            # the levels, each output conv one direct-convolution launch (lib/heads/retina_head.py:87)
+            (cls,) = ops.conv3x3_out_levels([self.retina_cls], ops.head_tower_levels(self.cls_convs, xs))
+            (reg,) = ops.conv3x3_out_levels([self.retina_reg], ops.head_tower_levels(self.reg_convs, xs))
+            return cls, reg
         cls = [self.retina_cls(self.cls_convs(x)) for x in xs]
         reg = [self.retina_reg(self.reg_convs(x)) for x in xs]
         return cls, reg

@@ -1533,6 +1533,192 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
     return outs
 
 
+# ---------------------------------------------------------------- one-stage head convolutions
+_CONV3X3_OUT_MAX_COUT = 192
+
+# The parts of a one-stage head at which tools/bench_head_convs.py measured the fused side slower
+# than the modules (both times in DESIGN section 4, "One-stage head convolutions"), keyed by what
+# was measured: ('tower', cin, cout) for a tower layer over the levels, ('out', cin, c0, c1) for an
+# output group.  A part is dispatched only where the fused side's slowest repetition beat the
+# modules' fastest; a part listed here keeps the modules for itself, the rest of the head stays
+# fused.
+_HEAD_CONVS_EXCLUDED = frozenset()
+
+
+def _conv3x3_plain(conv):
+    """A 3x3 / stride-1 / padding-1 Conv2d with a channels-last f32 weight and an f32 bias (or
+    none), both 16-byte aligned where the entries read them as vectors."""
+    return (isinstance(conv, nn.Conv2d) and _conv_is(conv, 3, 1, 1) and conv.in_channels % 8 == 0
+            and conv.weight.is_contiguous(memory_format=torch.channels_last) and _aligned16(conv.weight)
+            and (conv.bias is None or (conv.bias.dtype == torch.float32 and conv.bias.is_contiguous()
+                                       and _aligned16(conv.bias))))
+
+
+def _levels_ok(xs, cin):
+    """f32 HIP levels of one batch and device with cin channels at stride 1, at most 8, whose other
+    strides the *_levels entries take (non-negative multiples of 4)."""
+    if not xs or len(xs) > 8:
+        return False
+    x0 = xs[0]
+    for x in xs:
+        if not (_f32_hip_4d(x) and x.device == x0.device and x.shape[0] == x0.shape[0] and x.shape[1] == cin
+                and x.numel() > 0 and x.stride(1) == 1 and _aligned16(x)
+                and all(s >= 0 and s % 4 == 0 for i, (d, s) in enumerate(zip(x.shape, x.stride())) if i != 1 and d > 1)
+                and x.shape[0] * x.shape[2] * x.shape[3] < 1 << 27):
+            return False
+    return True
+
+
+def _out_group_ok(convs):
+    """One or two output convs frh_conv3x3_out_levels takes in one launch."""
+    return (1 <= len(convs) <= 2 and all(_conv3x3_plain(c) and c.in_channels == convs[0].in_channels for c in convs)
+            and sum(c.out_channels for c in convs) <= _CONV3X3_OUT_MAX_COUT)
+
+
+def _out_class(convs):
+    return ('out', convs[0].in_channels, convs[0].out_channels, convs[1].out_channels if len(convs) > 1 else 0)
+
+
+def conv3x3_out_fused_ok(convs, xs, scales=None):
+    """Whether conv3x3_out_levels takes the fused HIP entry for these arguments."""
+    convs, xs = list(convs), list(xs)
+    if not (_out_group_ok(convs) and _levels_ok(xs, convs[0].in_channels)) or _out_class(convs) in _HEAD_CONVS_EXCLUDED:
+        return False
+    flat = []
+    for k, conv in enumerate(convs):
+        sk = scales[k] if scales is not None else None
+        if sk is None:
+            continue
+        if len(sk) != len(xs):
+            return False
+        for s in sk:
+            if s is not None and not (s.is_cuda and s.dtype == torch.float32 and s.dim() == 1 and s.is_contiguous()
+                                      and s.numel() == conv.out_channels):
+                return False
+        flat += list(sk)
+    return not _needs_grad(*(xs + [c.weight for c in convs] + [c.bias for c in convs] + flat))
+
+
+def _conv_out_empty(conv, x):
+    """The output of conv for the level x, as the module would lay it out: the memory is
+    [n, h, w, c] either way; a one-pixel level is also NCHW-contiguous, and then the modules return
+    it with those strides."""
+    fmt = torch.channels_last if _suggests_channels_last(x) or _suggests_channels_last(conv.weight) \
+        else torch.contiguous_format
+    return torch.empty((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device,
+                       memory_format=fmt)
+
+
+def conv3x3_out_levels(convs, xs, scales=None, exp=False):
+    """The prediction convs of a one-stage head over every level: convs one Conv2d or a list of one
+    or two that read the same levels xs (3x3 / stride 1 / padding 1, at most 192 output channels
+    together); returns one list of per-level [n, c, h, w] channels-last tensors per conv,
+    [exp(conv(x) * scale)] with the scale and the exp optional per conv: scales None, or per conv
+    None or a list of per-level f32 [c] tensors (entries may be None); exp a bool, or one per conv.
+    One HIP launch (frh_conv3x3_out_levels: a direct f32-MFMA convolution, each level read once
+    for both convs, bias / scale / exp on the accumulators, one fixed-order sum per output) on
+    channel-stride-1 f32 HIP levels when nothing needs a gradient; otherwise the module
+    expressions."""
+    convs = [convs] if isinstance(convs, nn.Module) else list(convs)
+    xs = list(xs)
+    exps = [bool(exp)] * len(convs) if isinstance(exp, (bool, int)) else [bool(e) for e in exp]
+    if scales is not None:
+        scales = [None if s is None else list(s) for s in scales]
+    if len(exps) != len(convs) or (scales is not None and len(scales) != len(convs)):
+        raise AssertionError('conv3x3_out_levels: one scale list and one exp flag per conv')
+    if not conv3x3_out_fused_ok(convs, xs, scales):
+        outs = []
+        for k, conv in enumerate(convs):
+            ys = []
+            for i, x in enumerate(xs):
+                y = conv(x)
+                s = scales[k][i] if scales is not None and scales[k] is not None else None
+                if s is not None:
+                    y = y * s.view(-1, 1, 1)
+                ys.append(torch.exp(y) if exps[k] else y)
+            outs.append(ys)
+        return outs
+    ys = [[_conv_out_empty(conv, x) for x in xs] for conv in convs]
+    two = len(convs) == 2
+    c0, c1 = convs[0], convs[1] if two else None
+    sc = [None if scales is None or scales[k] is None else _ptrs_or_null(scales[k]) for k in range(len(convs))]
+    call('frh_conv3x3_out_levels', len(xs), ptr_array(xs), ptr_array(ys[0]), ptr_array(ys[1]) if two else None,
+         ptr(c0.weight), ptr(c0.bias), ptr(c1.weight) if two else None, ptr(c1.bias) if two else None,
+         sc[0], sc[1] if two else None, int(exps[0]), int(exps[1]) if two else 0, xs[0].shape[0], c0.in_channels,
+         c0.out_channels, c1.out_channels if two else 0, *_level_geometry(xs), stream_of(xs[0]))
+    return ys
+
+
+def _tower_convs(tower):
+    """The convs of a head tower (a Sequential of Conv2d, ReLU pairs), or None if it is anything else."""
+    mods = list(tower)
+    if len(mods) % 2 or not all(isinstance(c, nn.Conv2d) and isinstance(r, nn.ReLU)
+                                for c, r in zip(mods[0::2], mods[1::2])):
+        return None
+    return mods[0::2]
+
+
+def head_convs_fused_ok(tower_convs, out_convs, xs, extra=()):
+    """Whether a one-stage head runs its towers and output convs on the fused HIP entries
+    (head_tower_levels, conv3x3_out_levels) for these arguments; all or nothing per head.
+    tower_convs: the head's towers (each a Sequential of Conv2d, ReLU pairs); out_convs: one group of
+    one or two output convs per tower; xs: the levels; extra: further tensors of the forward
+    (FCOSHead's reg_coef).  True only for at most 8 f32 HIP levels with channel stride 1,
+    channels-last f32 weights, 3x3 / stride-1 / padding-1 tower convs each followed by a ReLU with
+    cin % 8 == 0 and cout % 64 == 0, output groups within frh_conv3x3_out_levels' limits, nothing
+    needing a gradient, and a head of which a part is dispatched at all (_HEAD_CONVS_EXCLUDED: a
+    listed part keeps its modules inside the fused forward)."""
+    xs = list(xs)
+    if not xs or not all(torch.is_tensor(x) and x.dim() == 4 for x in xs) or not _levels_ok(xs, xs[0].shape[1]):
+        return False
+    parts = _head_parts(tower_convs, out_convs, xs[0].shape[1])
+    if parts is None or all(p in _HEAD_CONVS_EXCLUDED for p, _ in parts):
+        return False
+    tensors = xs + list(extra)
+    for _, convs in parts:
+        for conv in convs:
+            tensors += [conv.weight, conv.bias]
+    return not _needs_grad(*tensors)
+
+
+def _head_parts(tower_convs, out_convs, cin):
+    """The parts of a head whose layers the fused entries can run on cin-channel levels, as
+    (class, convs) pairs in forward order -- ('tower', cin, cout) per tower layer, ('out', cin, c0,
+    c1) per output group -- or None where a layer is outside them (the device, the levels and the
+    gradients are head_convs_fused_ok's to check)."""
+    towers, groups = list(tower_convs), [list(g) for g in out_convs]
+    if len(towers) != len(groups):
+        return None
+    parts = []
+    for tower, group in zip(towers, groups):
+        convs = _tower_convs(tower)
+        if convs is None:
+            return None
+        c = cin
+        for conv in convs:
+            if not (_conv3x3_plain(conv) and conv.in_channels == c and conv.out_channels % 64 == 0):
+                return None
+            parts.append((('tower', conv.in_channels, conv.out_channels), [conv]))
+            c = conv.out_channels
+        if not _out_group_ok(group) or group[0].in_channels != c:
+            return None
+        parts.append((_out_class(group), group))
+    return parts
+
+
+def head_tower_levels(tower, xs):
+    """[tower(x) for x in xs] for a head tower head_convs_fused_ok accepted: layer by layer, one
+    conv3x3_bias_act_levels call (the conv shared over the levels, bias + ReLU on the Winograd
+    accumulators); a layer class listed in _HEAD_CONVS_EXCLUDED runs its modules."""
+    xs = list(xs)
+    for conv in _tower_convs(tower):
+        if ('tower', conv.in_channels, conv.out_channels) in _HEAD_CONVS_EXCLUDED:
+            xs = [torch.relu(conv(x)) for x in xs]
+        else:
+            xs = conv3x3_bias_act_levels(conv, xs, relu=True)
+    return xs
+
+
 # Channel classes (cin, cout) at which tools/bench_conv3x3_nchw.py measured frh_conv3x3_nchw_bn_act
 # (weight transform included) slower than MIOpen's NCHW 3x3 conv, plus frh_bn_act where the
 # entry's epilogue replaces one (both times in DESIGN section 4): they keep the module.  A class
