@@ -31,14 +31,10 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
-sys.path.insert(0, HERE)
+from benchlib import REPO, limit, max_rel_diff, measure, put_times, require_gpu, wins, write_json
 
 N = 2
 # (cin, cout, hw, launches per step, skip, relu, where)
@@ -61,20 +57,7 @@ SHAPES = [
 PRE_SHAPES = [(64, 256, 38912, 3), (128, 512, 9728, 4), (256, 1024, 2432, 6), (512, 2048, 608, 3)]
 # the stride-2 projections (cin, cout, input h, input w), one per step each
 S2_SHAPES = [(256, 512, 152, 256), (512, 1024, 76, 128), (1024, 2048, 38, 64)]
-PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
 SETS = 3
-
-
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def _bn(c, dev):
@@ -135,35 +118,21 @@ def input_forms(mode, out, iters=20, reps=7):
                 return lambda: _lib.call('frh_conv1x1_s2_bn_act', p(xs[i]), p(conv.weight), None, p(ys[i]),
                                          *_bn_ptrs(bn), N, cin, cout, h, w, 0, st)
             sides = {'parent': [parent(i) for i in range(SETS)], 'new': [new(i) for i in range(SETS)]}
-            for fns in sides.values():
-                for f in fns:
-                    f()
-                    f()
-            torch.cuda.synchronize()
-            maxdiff = float((yp[0] - ys[0]).abs().max() / yp[0].abs().max())
-            t = {k: [] for k in sides}
-            for _ in range(reps):
-                for k, fns in sides.items():
-                    t[k].append(time_calls(fns, iters))
-            stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
+            stat = measure(sides, iters, reps, warmup=2)
+            maxdiff = max_rel_diff(yp[0], ys[0])
             row = {'cin': cin, 'cout': cout, 'input_hw': [h, w], 'launches_per_step': count,
-                   'max_rel_diff_vs_parent': maxdiff, 'new_wins': stat['new'][2] < stat['parent'][1],
-                   'parent_wins': stat['parent'][2] < stat['new'][1]}
-            for k, (med, lo, hi) in stat.items():
-                row[k + '_us'] = round(med, 1)
-                row[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
-            rows.append(row)
+                   'max_rel_diff_vs_parent': maxdiff, 'new_wins': wins(stat, 'new', 'parent'),
+                   'parent_wins': wins(stat, 'parent', 'new')}
+            rows.append(put_times(row, stat, 1))
             print('{} {:5d}->{:4d} @ {}x{} x{}  parent {:7.1f} us [{:.1f}, {:.1f}]  new {:7.1f} us [{:.1f}, {:.1f}]  '
-                  'new wins {}  diff {:.1e}'.format(mode, cin, cout, h, w, count, *stat['parent'], *stat['new'],
+                  'new wins {}  diff {:.1e}'.format(mode, cin, cout, h, w, count, *stat['parent'][:3], *stat['new'][:3],
                                                    row['new_wins'], maxdiff), flush=True)
             del xs, mids, sk, ys, yp
     res = {'device': torch.cuda.get_device_name(0), 'mode': mode, 'iters': iters, 'reps': reps, 'batch': N,
            'shapes': rows,
            'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
            'per_step_new_us': round(sum(r['new_us'] * r['launches_per_step'] for r in rows), 1)}
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(out, res)
     print(json.dumps({k: v for k, v in res.items() if k != 'shapes'}))
 
 
@@ -173,8 +142,7 @@ def main():
     ap.add_argument('--mode', default='stride1', choices=['stride1', 'pre', 's2'])
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_conv1x1 needs a HIP device')
+    require_gpu('bench_conv1x1')
     if args.mode != 'stride1':
         return input_forms(args.mode, args.out or os.path.join(REPO, 'profiles', 'small_passes',
                                                                'bench_conv1x1_{}.json'.format(args.mode)))
@@ -220,28 +188,18 @@ def main():
             if tools is not None:
                 for t in (16, 32):
                     sides['step{}'.format(t)] = [entry(i, t) for i in range(SETS)]
-            for fns in sides.values():
-                for f in fns:
-                    f()
-                    f()
-            torch.cuda.synchronize()
-            ref, got = sides['parent'][0](), ys[0]
+            med = {k: s.median for k, s in measure(sides, args.iters, 3, warmup=2).items()}
+            ref = sides['parent'][0]()
             sides['fused'][0]()
-            maxdiff = float((ref - got).abs().max() / ref.abs().max())
-            t = {k: [] for k in sides}
-            for _ in range(3):
-                for k, fns in sides.items():
-                    t[k].append(time_calls(fns, args.iters))
-            med = {k: float(np.median(v)) for k, v in t.items()}
+            maxdiff = max_rel_diff(ref, ys[0])
             flops = 2.0 * N * cin * cout * hw
             nbytes = 4.0 * (N * hw * (cin + cout * (2 if skip else 1)) + cin * cout)
-            limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
+            limit_us, bound = limit(flops, nbytes)
             row = {'where': where, 'cin': cin, 'cout': cout, 'hw': hw, 'launches_per_step': count, 'skip': skip,
                    'relu': relu, 'excluded_in_ops': (cin, cout) in ops._CONV1X1_EXCLUDED, 'parent_us': round(med['parent'], 2), 'fused_us': round(med['fused'], 2),
                    'steps_us': {k: round(v, 2) for k, v in med.items() if k.startswith('step')},
                    'gflop': round(flops / 1e9, 3), 'algorithmic_MB': round(nbytes / 1e6, 2),
-                   'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
-                   'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / med['fused'], 3),
+                   'limit': bound, 'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / med['fused'], 3),
                    'fused_TFLOPs': round(flops / med['fused'] / 1e6, 1), 'fused_TBps': round(nbytes / med['fused'] / 1e6, 2),
                    'max_rel_diff_vs_parent': maxdiff}
             rows.append(row)
@@ -252,9 +210,7 @@ def main():
     res = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'batch': N, 'shapes': rows,
            'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
            'per_step_fused_us': round(sum(r['fused_us'] * r['launches_per_step'] for r in rows), 1)}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps({k: v for k, v in res.items() if k != 'shapes'}))
 
 

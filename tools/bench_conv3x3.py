@@ -22,44 +22,18 @@ bytes / 8 TB/s."""
 import argparse
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import REPO, limit, max_rel_diff, measure, require_gpu, write_json
 
 N, C = 2, 256
 LEVELS = [('P2', 152, 256), ('P3', 76, 128), ('P4', 38, 64), ('P5', 19, 32), ('P6', 10, 16)]
-PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
 SETS = 3
 
 
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def measure(sides, iters):
-    for fns in sides.values():
-        for f in fns:
-            f()
-            f()
-    torch.cuda.synchronize()
-    t = {k: [] for k in sides}
-    for _ in range(3):
-        for k, fns in sides.items():
-            t[k].append(time_calls(fns, iters))
-    return {k: float(np.median(v)) for k, v in t.items()}
+def medians(sides, iters):
+    return {k: s.median for k, s in measure(sides, iters, 3, warmup=2).items()}
 
 
 def main():
@@ -69,8 +43,7 @@ def main():
     ap.add_argument('--fused-only', action='store_true',
                     help='time only the fused entries (no MIOpen side, no search): for counter passes')
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_conv3x3 needs a HIP device')
+    require_gpu('bench_conv3x3')
     from frcnn_amd import _lib, ops
     from frcnn_amd.utils import conv_layout
     torch.backends.cudnn.benchmark = True
@@ -110,21 +83,20 @@ def main():
                 sides = {'parent': parent, 'fused': [entry(x, y, relu) for x, y in zip(xs, ys)]}
                 if args.fused_only:
                     del sides['parent']
-                med = measure(sides, args.iters)
+                med = medians(sides, args.iters)
                 med.setdefault('parent', float('nan'))
                 maxdiff = float('nan')
                 if not args.fused_only:
                     ref = parent[0]()
                     sides['fused'][0]()
-                    maxdiff = float((ref - ys[0]).abs().max() / ref.abs().max())
+                    maxdiff = max_rel_diff(ref, ys[0])
                 flops = 2.0 * 16 * N * ((h + 1) // 2) * ((w + 1) // 2) * C * C
                 nbytes = 4.0 * (2 * N * h * w * C + 9 * C * C)
-                limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
+                limit_us, bound = limit(flops, nbytes)
                 row = {'level': name, 'h': h, 'w': w, 'form': form, 'excluded_in_ops': (h, w) in ops._CONV3X3_EXCLUDED,
                        'parent_us': round(med['parent'], 2), 'fused_us': round(med['fused'], 2),
                        'winograd_gflop': round(flops / 1e9, 3), 'direct_gflop': round(flops * 2.25 / 1e9, 3),
-                       'algorithmic_MB': round(nbytes / 1e6, 2),
-                       'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
+                       'algorithmic_MB': round(nbytes / 1e6, 2), 'limit': bound,
                        'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / med['fused'], 3),
                        'fused_winograd_TFLOPs': round(flops / med['fused'] / 1e6, 1),
                        'max_rel_diff_vs_parent': maxdiff}
@@ -158,7 +130,7 @@ def main():
                  'per_level': [per_level_all(i) for i in range(SETS)]}
         if args.fused_only:
             del sides['parent']
-        med = measure(sides, args.iters)
+        med = medians(sides, args.iters)
         med.setdefault('parent', float('nan'))
         head = {k + '_us': round(v, 2) for k, v in med.items()}
         print('RPN head, five levels: parent {parent_us} us, one launch {levels_us} us, five launches {per_level_us} us'
@@ -184,7 +156,7 @@ def main():
         sides = {'parent': [fpn_parent(i) for i in range(SETS)], 'levels': [fpn_levels(i) for i in range(SETS)]}
         if args.fused_only:
             del sides['parent']
-        med = measure(sides, args.iters)
+        med = medians(sides, args.iters)
         med.setdefault('parent', float('nan'))
         neck = {k + '_us': round(v, 2) for k, v in med.items()}
         print('FPN output convs, four levels: parent {parent_us} us, one launch {levels_us} us'.format(**neck),
@@ -194,9 +166,7 @@ def main():
            'rpn_head_five_levels': head, 'fpn_outputs_four_levels': neck,
            'fpn_outputs_parent_us': round(sum(r['parent_us'] for r in fpn), 1),
            'fpn_outputs_fused_us': round(sum(r['fused_us'] for r in fpn), 1)}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps({k: v for k, v in res.items() if k != 'levels'}))
 
 

@@ -23,14 +23,10 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
-sys.path.insert(0, HERE)
+from benchlib import REPO, limit, max_rel_diff, measure, put_times, require_gpu, wins, write_json
 
 N = 2
 # (cin = cout, h, w, launches per step, bn2 + ReLU in the epilogue, where)
@@ -40,23 +36,10 @@ CLASSES = [
     (256, 38, 64, 5, False, 'stage 3 conv2'),
     (512, 19, 32, 2, True, 'stage 4 conv2'),
 ]
-PEAK_FLOPS, PEAK_BYTES = 157.3e12, 8.0e12
 SETS, ITERS, REPS = 3, 20, 7
 # 0 .. 2: (NT, NC), one wave per work item; 3, 4: cin split S over a workgroup of S x TR waves (the
 # product's forms); 5 ..: the laboratory forms with U through LDS (tools/csrc/conv3x3_nchw_lab.hip)
 FORMS = ['(2, 1)', '(1, 2)', '(1, 1)', 'NC1 S4 TR1', 'NC1 S2 TR2', 'NC2 S1 TR4 lds', 'NC1 S2 TR2 lds', 'NC1 S1 TR4 lds']
-
-
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def main():
@@ -69,8 +52,7 @@ def main():
     ap.add_argument('--sides', default='', help='comma-separated subset of parent,fused,form0.. (a counter pass '
                     'times few launches of few sides; the parent and fused sides are needed for the comparison fields)')
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_conv3x3_nchw needs a HIP device')
+    require_gpu('bench_conv3x3_nchw')
     from frcnn_amd import _lib, ops
     try:
         import toolslib
@@ -133,39 +115,26 @@ def main():
                     sides['form{}'.format(f)] = [entry(i, f) for i in range(SETS)]
             if args.sides:
                 sides = {k: v for k, v in sides.items() if k in ('parent', 'fused', 'parent_lib') or k in args.sides.split(',')}
-            for fns in sides.values():
-                for f in fns:
-                    f()
-                    f()
-            torch.cuda.synchronize()
+            stat = measure(sides, args.iters, args.reps, warmup=2)
             sides['parent'][0]()
             sides['fused'][0]()
-            torch.cuda.synchronize()
-            maxdiff = float((yp[0] - ys[0]).abs().max() / yp[0].abs().max())
-            t = {k: [] for k in sides}
-            for _ in range(args.reps):
-                for k, fns in sides.items():
-                    t[k].append(time_calls(fns, args.iters))
-            stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
+            maxdiff = max_rel_diff(yp[0], ys[0])
             flops = 2.0 * 16 * N * c * c * ((h + 1) // 2) * ((w + 1) // 2)
             nbytes = 4.0 * (2 * N * c * h * w + 9 * c * c)
-            limit_us = max(flops / PEAK_FLOPS, nbytes / PEAK_BYTES) * 1e6
+            limit_us, bound = limit(flops, nbytes)
             row = {'where': where, 'cin': c, 'cout': c, 'hw': [h, w], 'launches_per_step': count,
                    'bn_relu_epilogue': epi, 'excluded_in_ops': (c, c) in ops._CONV3X3_NCHW_EXCLUDED,
-                   'fused_wins': stat['fused'][2] < stat['parent'][1],
-                   'fused_beats_parent_lib': stat['fused'][2] < stat['parent_lib'][1] if plib is not None else None,
+                   'fused_wins': wins(stat, 'fused', 'parent'),
+                   'fused_beats_parent_lib': wins(stat, 'fused', 'parent_lib') if plib is not None else None,
                    'winograd_gflop': round(flops / 1e9, 3), 'algorithmic_MB': round(nbytes / 1e6, 2),
-                   'limit': 'compute' if flops / PEAK_FLOPS > nbytes / PEAK_BYTES else 'bandwidth',
+                   'limit': bound,
                    'limit_us': round(limit_us, 2), 'fused_share_of_limit': round(limit_us / stat['fused'][0], 3),
                    'parent_share_of_limit': round(limit_us / stat['parent'][0], 3),
                    'max_rel_diff_vs_parent': maxdiff}
-            for k, (med, lo, hi) in stat.items():
-                row[k + '_us'] = round(med, 1)
-                row[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
-            rows.append(row)
+            rows.append(put_times(row, stat, 1))
             print('{:14s} {:4d}->{:4d} @ {}x{} x{}  parent {:7.1f} [{:.1f}, {:.1f}]  fused {:7.1f} [{:.1f}, {:.1f}]  {}  '
                   'limit {:.1f} us  wins {}  diff {:.1e}'.format(
-                      where, c, c, h, w, count, *stat['parent'], *stat['fused'],
+                      where, c, c, h, w, count, *stat['parent'][:3], *stat['fused'][:3],
                       {k: round(v[0], 1) for k, v in stat.items() if k.startswith('form')}, limit_us,
                       row['fused_wins'], maxdiff), flush=True)
             del xs, ys, yp
@@ -173,9 +142,7 @@ def main():
            'classes': rows,
            'per_step_parent_us': round(sum(r['parent_us'] * r['launches_per_step'] for r in rows), 1),
            'per_step_fused_us': round(sum(r['fused_us'] * r['launches_per_step'] for r in rows), 1)}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps({k: v for k, v in res.items() if k != 'classes'}))
 
 

@@ -16,32 +16,15 @@ tensor sets in rotation, the weight transform included); `reps` repetitions, the
 sides reversed on every other one; median [min, max] per side and shape."""
 import argparse
 import ctypes
-import json
 import os
-import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import REPO, measure, require_gpu, write_json
 
 N, C = 2, 256
 LEVELS = [('P2', 152, 256), ('P3', 76, 128), ('P4', 38, 64), ('P5', 19, 32), ('P6', 10, 16)]
 SETS = 3
-
-
-def time_calls(fns, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def main():
@@ -52,8 +35,7 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'conv3x3_issue', 'bench_conv3x3_variants.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_conv3x3_variants needs a HIP device')
+    require_gpu('bench_conv3x3_variants')
     from frcnn_amd import _lib
     from frcnn_amd.utils import conv_layout
     import toolslib
@@ -119,18 +101,13 @@ def main():
                     for o, want in zip(outs[s][i], outs['product'][i]):
                         if not torch.equal(o, want):
                             raise SystemExit('{} {}: output differs from the product kernel'.format(s, shape))
-            t = {s: [] for s in sides}
-            for rep in range(args.reps):
-                for s in (sides if rep % 2 == 0 else sides[::-1]):
-                    t[s].append(time_calls(fns[s], args.iters))
-            row = {s: {'median_us': round(float(np.median(v)), 2), 'min_us': round(min(v), 2),
-                       'max_us': round(max(v), 2), 'all_us': [round(x, 2) for x in v]} for s, v in t.items()}
+            row = {s: {'median_us': round(v.median, 2), 'min_us': round(v.min, 2), 'max_us': round(v.max, 2),
+                       'all_us': [round(x, 2) for x in v.runs]}
+                   for s, v in measure(fns, args.iters, args.reps, warmup=0, reverse=True).items()}
             res['shapes'][shape] = row
             print(shape, '  '.join('{} {:.1f} [{:.1f}, {:.1f}]'.format(s, r['median_us'], r['min_us'], r['max_us'])
                                    for s, r in row.items()), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
 
 
 if __name__ == '__main__':

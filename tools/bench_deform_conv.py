@@ -24,48 +24,29 @@ TFLOP/s and its share of the 157.3 TFLOP/s f32-matrix peak (a whole-call rate: b
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import PEAK_FLOPS, REPO, max_rel_diff, measure, put_times, require_gpu, wins, write_json
 
 CIN = COUT = 256
 DG = 4
 BATCH = 2
 LEVELS = [(152, 256), (76, 128), (38, 64), (19, 32), (10, 16)]
-PEAK_FLOPS = 157.3e12
 SETS = 3
 
 
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def measure(sides, iters, reps):
-    """{side: {'warm': (median, min, max), 'cold': ...}} in us; sides: {name: ([fn per set], iters scale)}."""
-    out = {}
-    t = {(k, m): [] for k in sides for m in ('warm', 'cold')}
-    for _ in range(reps):
-        for k, (fns, scale) in sides.items():
-            n = max(1, iters // scale)
-            t[(k, 'warm')].append(time_calls(fns[:1], n))
-            t[(k, 'cold')].append(time_calls(fns, max(n, len(fns))))
-    for (k, m), v in t.items():
-        out.setdefault(k, {})[m] = (float(np.median(v)), float(min(v)), float(max(v)))
-    return out
+def warm_and_cold(sides, iters, reps):
+    """{'<side>_warm' / '<side>_cold': Stat}; sides: {name: ([fn per set], iters scale)}.  Per
+    repetition and side a warm window (set 0 only) and then a cold one (the sets in rotation)."""
+    windows, n = {}, {}
+    for k, (fns, scale) in sides.items():
+        base = max(1, iters // scale)
+        windows[k + '_warm'], n[k + '_warm'] = fns[:1], base
+        windows[k + '_cold'], n[k + '_cold'] = fns, max(base, len(fns))
+    return measure(windows, n, reps, warmup=0)
 
 
 def step_times(dev, reps):
@@ -108,8 +89,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'ga_rpn', 'bench_deform_conv.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_deform_conv needs a HIP device')
+    require_gpu('bench_deform_conv')
     from frcnn_amd import ops
     torch.backends.cudnn.benchmark = True
     dev = torch.device('cuda', 0)
@@ -138,14 +118,10 @@ def main():
         def report(tag, positions, stat, extra):
             flops = 2.0 * positions * 9 * CIN * COUT
             row = dict(extra, shape=tag, positions=positions, gflop=round(flops / 1e9, 2))
-            for k, v in stat.items():
-                for m, (med, lo, hi) in v.items():
-                    row['{}_{}_us'.format(k, m)] = round(med, 1)
-                    row['{}_{}_us_min_max'.format(k, m)] = [round(lo, 1), round(hi, 1)]
-            row['hip_wins'] = stat['hip']['cold'][2] < stat['torch']['cold'][1]
-            row['hip_over_conv_cold'] = round(stat['hip']['cold'][0] / stat['conv']['cold'][0], 2)
-            row['hip_TFLOPs_cold'] = round(flops / stat['hip']['cold'][0] / 1e6, 1)
-            row['hip_share_of_f32_matrix_peak'] = round(flops / stat['hip']['cold'][0] / 1e6 / (PEAK_FLOPS / 1e12), 3)
+            put_times(row, stat, 1)['hip_wins'] = wins(stat, 'hip_cold', 'torch_cold')
+            row['hip_over_conv_cold'] = round(stat['hip_cold'][0] / stat['conv_cold'][0], 2)
+            row['hip_TFLOPs_cold'] = round(flops / stat['hip_cold'][0] / 1e6, 1)
+            row['hip_share_of_f32_matrix_peak'] = round(flops / stat['hip_cold'][0] / 1e6 / (PEAK_FLOPS / 1e12), 3)
             rows.append(row)
             print(tag, {k: row[k] for k in ('hip_cold_us', 'hip_warm_us', 'torch_cold_us', 'conv_cold_us', 'hip_wins',
                                             'hip_over_conv_cold', 'hip_share_of_f32_matrix_peak')}, flush=True)
@@ -158,10 +134,10 @@ def main():
                     f()
             torch.cuda.synchronize()
             a, b = sides['hip'][0][0](), sides['torch'][0][0]()
-            diff = float((a - b).abs().max() / b.abs().max())
+            diff = max_rel_diff(b, a)
             fused = bool(ops.deform_conv3x3_fused_ok(xs[0][l], ss[0][l], w, DG, ow))
             del a, b
-            report('{}x{}'.format(h, wd), BATCH * h * wd, measure(sides, args.iters, args.reps),
+            report('{}x{}'.format(h, wd), BATCH * h * wd, warm_and_cold(sides, args.iters, args.reps),
                    {'fused_in_ops': fused, 'max_rel_diff_vs_torch': diff})
 
         sides = {
@@ -172,15 +148,13 @@ def main():
         for fns, _ in sides.values():
             fns[0]()
         torch.cuda.synchronize()
-        report('pyramid', BATCH * sum(h * wd for h, wd in LEVELS), measure(sides, args.iters, args.reps),
+        report('pyramid', BATCH * sum(h * wd for h, wd in LEVELS), warm_and_cold(sides, args.iters, args.reps),
                {'launches': 'one repack + one convolution for the five levels'})
     res = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'reps': args.reps, 'cin': CIN, 'cout': COUT,
            'deformable_groups': DG, 'batch': BATCH, 'shapes': rows}
     if not args.no_step:
         res['forward_test_step'] = step_times(dev, args.reps)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

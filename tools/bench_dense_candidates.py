@@ -24,24 +24,17 @@ tenth of the iterations.  The selected column sets of the two sides are compared
 import argparse
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
-sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
-sys.path.insert(0, HERE)
+from benchlib import PEAK_BYTES, REPO, compare, count_launches, count_syncs, on_path, require_gpu, write_json
 
-from bench_fcos import compare, count_launches, count_syncs  # noqa: E402
+on_path('tests', 'golden')
 
 IMG_SHAPE, PAD = (800, 1333), (800, 1344)
 STRIDES = [8, 16, 32, 64, 128]
 GRIDS = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
 B, C, PRE_NMS = 2, 20, 1000
-HBM_GBPS = 8000.0
 
 
 def main():
@@ -49,8 +42,7 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'dense_candidates', 'bench_dense_candidates.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_dense_candidates needs a HIP device')
+    require_gpu('bench_dense_candidates')
     import dense_inputs as di
     from frcnn_amd import ops
     from frcnn_amd.config import ConfigDict
@@ -125,10 +117,10 @@ def main():
                 a_ = torch.sort(fo[1][b][fo[3][b]].max(1)[0])[0]
                 b_ = torch.sort(sc.max(0)[0])[0]
                 diff = max(diff, float((a_ - b_).abs().max()) if a_.shape == b_.shape else float('inf'))
-            th, tt, ah, at = compare(fused, loop, args.iters, max(args.iters // 10, 3))
+            th, tt, ah, at = compare(fused, loop, args.iters, max(args.iters // 10, 3), warmup=3)
             r = {'hip_us': round(th, 2), 'torch_us': round(tt, 2), 'hip_runs_us': ah, 'torch_runs_us': at,
                  'speedup': round(tt / th, 2), 'hip_GBps': round((read + written) / th / 1e3, 1),
-                 'hip_fraction_of_8TBps': round((read + written) / th / 1e3 / HBM_GBPS, 4),
+                 'hip_fraction_of_8TBps': round((read + written) / th / 1e3 / (PEAK_BYTES / 1e9), 4),
                  'largest_best_score_difference_of_the_selected_rows': diff,
                  'launches_and_syncs': {'hip': [count_launches(fused), count_syncs(fused)],
                                         'torch': [count_launches(loop), count_syncs(loop)],
@@ -138,9 +130,7 @@ def main():
             out[layout] = r
             print(name, layout, json.dumps(r), flush=True)
         res[name] = out
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f_:
-        json.dump(res, f_, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

@@ -25,83 +25,25 @@ the three gradient tensors written once."""
 import argparse
 import json
 import os
-import sys
-import warnings
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
-sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
+from benchlib import PEAK_BYTES, REPO, compare, count_launches, count_syncs, on_path, require_gpu, write_json
+
+on_path('tests', 'golden')
 
 IMG_SHAPE, PAD = (800, 1333), (800, 1344)
 STRIDES = [8, 16, 32, 64, 128]
 GRIDS = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
 B, C, REG_STD, REG_MEAN = 2, 20, 1200.0, 0.0
 GT_COUNTS = (8, 40)
-HBM_GBPS = 8000.0
-
-
-def time_calls(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters  # us per call
-
-
-def compare(a, b, iters_a, iters_b, reps=5):
-    """us per call of a and b, alternating: (median a, median b, all a, all b)."""
-    for _ in range(3):
-        a()
-        b()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for _ in range(reps):
-        ta.append(time_calls(a, iters_a))
-        tb.append(time_calls(b, iters_b))
-    return float(np.median(ta)), float(np.median(tb)), [round(v, 2) for v in ta], [round(v, 2) for v in tb]
 
 
 def row(th, tt, ah, at, nbytes):
     return {'hip_us': round(th, 2), 'torch_us': round(tt, 2), 'hip_runs_us': ah, 'torch_runs_us': at,
             'speedup': round(tt / th, 2), 'algorithmic_bytes': int(nbytes), 'hip_GBps': round(nbytes / th / 1e3, 1),
-            'hip_fraction_of_8TBps': round(nbytes / th / 1e3 / HBM_GBPS, 4)}
-
-
-def count_launches(fn):
-    """Device kernels of one call (None when the profiler gives no device activity here)."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA')
-                and 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower())
-        return n or None
-    except Exception as exc:  # the profiler is optional equipment of this tool
-        print('profiler unavailable: {}'.format(exc), file=sys.stderr)
-        return None
-
-
-def count_syncs(fn):
-    fn()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode('warn')
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter('always')
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
-    torch.cuda.synchronize()
-    return sum(1 for x in w if 'synchroniz' in str(x.message).lower())
+            'hip_fraction_of_8TBps': round(nbytes / th / 1e3 / (PEAK_BYTES / 1e9), 4)}
 
 
 def main():
@@ -109,8 +51,7 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'fcos', 'bench_fcos.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_fcos needs a HIP device')
+    require_gpu('bench_fcos')
     import inputs
     from frcnn_amd import ops
     from frcnn_amd.heads import fcos_head as head_mod
@@ -145,7 +86,7 @@ def main():
         npos = int((labels > 0).sum())
         out = {'gts_per_image': G, 'positives': npos, 'ignored': int((labels < 0).sum()),
                'assign_labels_and_ltrb_equal_torch': bool(same), 'assign_largest_centerness_difference': ctr_diff}
-        out['assign'] = row(*compare(assign_hip, assign_torch, args.iters, max(args.iters // 20, 3)), 28 * M)
+        out['assign'] = row(*compare(assign_hip, assign_torch, args.iters, max(args.iters // 20, 3), warmup=3), 28 * M)
         out['assign']['note'] = 'torch: the per-image loop over gts and levels, two images'
 
         cls = torch.randn(C, M, device=dev, requires_grad=True)
@@ -166,7 +107,7 @@ def main():
         fbytes = 4 * C * M + 8 * M + npos * (16 + 16 + 4 + 4)
         bbytes = 2 * fbytes + 4 * C * M + 16 * M + 4 * M
         hip, tor = fwd_bwd(head.calc_loss_flat), fwd_bwd(head.calc_loss_modules)
-        out['loss_forward_backward'] = row(*compare(hip, tor, args.iters, max(args.iters // 4, 3)), bbytes)
+        out['loss_forward_backward'] = row(*compare(hip, tor, args.iters, max(args.iters // 4, 3), warmup=3), bbytes)
         out['loss_forward_backward']['note'] = ('includes the grad reset, the sum of the three losses and autograd on '
                                                 'both sides')
         out['launches_and_syncs'] = {
@@ -177,9 +118,7 @@ def main():
             'columns': ['device kernels per call (null: no device activity from the profiler)', 'host syncs per call']}
         res['gts_{}'.format(G)] = out
         print('gts', G, json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f_:
-        json.dump(res, f_, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

@@ -23,16 +23,13 @@ written once; decode the regression logits read and the boxes written once."""
 import argparse
 import json
 import os
-import sys
-import warnings
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
-sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
+from benchlib import PEAK_BYTES, REPO, compare, count_launches, count_syncs, on_path, require_gpu, write_json
+
+on_path('tests', 'golden')
 
 IMG = (800, 1344)
 STRIDES = [8, 16, 32, 64, 128]
@@ -40,67 +37,12 @@ GRIDS = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
 B, C, BINS, DFL_STRIDE, REG_STD, REG_MEAN = 2, 20, 16, 0.08, 1200.0, 0.0
 KW = dict(bins=BINS, stride=DFL_STRIDE, reg_mean=REG_MEAN, reg_std=REG_STD, norm_prob=False, beta=2.0,
           cls_weight=1.0, dfl_weight=0.25, bbox_weight=2.0, dfl_avg_factor=4.0)
-HBM_GBPS = 8000.0
-
-
-def time_calls(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters  # us per call
-
-
-def compare(a, b, iters, reps=5):
-    """us per call of a and b, alternating: (median a, median b, all a, all b)."""
-    for _ in range(5):
-        a()
-        b()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for _ in range(reps):
-        ta.append(time_calls(a, iters))
-        tb.append(time_calls(b, iters))
-    return float(np.median(ta)), float(np.median(tb)), [round(v, 2) for v in ta], [round(v, 2) for v in tb]
 
 
 def row(th, tt, ah, at, nbytes):
     return {'hip_us': round(th, 2), 'torch_us': round(tt, 2), 'hip_runs_us': ah, 'torch_runs_us': at,
             'speedup': round(tt / th, 2), 'algorithmic_bytes': int(nbytes), 'hip_GBps': round(nbytes / th / 1e3, 1),
-            'hip_fraction_of_8TBps': round(nbytes / th / 1e3 / HBM_GBPS, 4)}
-
-
-def count_launches(fn):
-    """Device kernels of one call (None when the profiler gives no device activity here)."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        fn()
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA')
-                and 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower())
-        return n or None
-    except Exception as exc:  # the profiler is optional equipment of this tool
-        print('profiler unavailable: {}'.format(exc), file=sys.stderr)
-        return None
-
-
-def count_syncs(fn):
-    fn()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode('warn')
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter('always')
-            fn()
-    finally:
-        torch.cuda.set_sync_debug_mode('default')
-    torch.cuda.synchronize()
-    return sum(1 for x in w if 'synchroniz' in str(x.message).lower())
+            'hip_fraction_of_8TBps': round(nbytes / th / 1e3 / (PEAK_BYTES / 1e9), 4)}
 
 
 def torch_decode(head_mod, utils, r, cell, img_size):
@@ -116,8 +58,7 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'gfl', 'bench_gfl.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_gfl needs a HIP device')
+    require_gpu('bench_gfl')
     import inputs
     from frcnn_amd import ops, utils
     from frcnn_amd.heads import fcos_head as head_mod
@@ -164,9 +105,10 @@ def main():
         return run
     fbytes = 4 * C * M + 8 * M + npos * (4 * 4 * BINS + 16 + 4 * C)
     bbytes = 2 * fbytes + 4 * C * M + 4 * 4 * BINS * M
-    res['loss_forward'] = row(*compare(fwd(ops.gfl_losses), fwd(gfl_head_losses_torch), args.iters), fbytes)
-    res['loss_forward_backward'] = row(*compare(fwd_bwd(ops.gfl_losses), fwd_bwd(gfl_head_losses_torch),
-                                                max(args.iters // 2, 10)), bbytes)
+    res['loss_forward'] = row(*compare(fwd(ops.gfl_losses), fwd(gfl_head_losses_torch), args.iters, args.iters, warmup=5), fbytes)
+    half = max(args.iters // 2, 10)
+    res['loss_forward_backward'] = row(*compare(fwd_bwd(ops.gfl_losses), fwd_bwd(gfl_head_losses_torch), half, half,
+                                                warmup=5), bbytes)
     res['loss_forward_backward']['note'] = 'includes the grad reset, the sum of the three losses and autograd on both sides'
 
     levels = [torch.randn(B, 4 * BINS, h, w, device=dev).contiguous(memory_format=torch.channels_last)
@@ -182,7 +124,7 @@ def main():
             for lv, s in zip(levels, STRIDES):
                 torch_decode(head_mod, utils, lv[i], s, IMG)
     dbytes = (4 * 4 * BINS + 16) * M
-    res['decode'] = row(*compare(dec_hip, dec_torch, args.iters), dbytes)
+    res['decode'] = row(*compare(dec_hip, dec_torch, args.iters, args.iters, warmup=5), dbytes)
     res['decode']['note'] = 'ten calls: two images x five levels, as FCOSHead.image_candidates decodes'
     err = max(float((ops.dfl_decode(lv[:1], BINS, DFL_STRIDE, REG_STD, REG_MEAN, s, IMG)[0]
                      - torch_decode(head_mod, utils, lv[0], s, IMG)).abs().max()) for lv, s in zip(levels, STRIDES))
@@ -198,9 +140,7 @@ def main():
         'decode': {'hip': [count_launches(dec_hip), count_syncs(dec_hip)],
                    'torch': [count_launches(dec_torch), count_syncs(dec_torch)]},
         'columns': ['device kernels per call (null: no device activity from the profiler)', 'host syncs per call']}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f_:
-        json.dump(res, f_, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

@@ -24,57 +24,29 @@ the 157.3 TFLOP/s f32 MFMA peak the fused side reaches."""
 import argparse
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 from torch import nn
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import PEAK_BYTES, PEAK_FLOPS, REPO, max_rel_diff, measure, put_times, require_gpu, wins, write_json
 
 N, CIN, CLASSES, BINS = 2, 256, 20, 16
 LEVELS = ((76, 128), (38, 64), (19, 32), (10, 16), (5, 8))
-PEAK_BYTES, PEAK_FLOPS = 8.0e12, 157.3e12
 SETS = 12
 OUT_GROUPS = (('retina_cls', (9 * CLASSES,), None), ('retina_reg', (36,), None), ('fcos_cls', (CLASSES,), None),
               ('fcos_reg_ctr', (4, 1), 'exp'), ('gfl_reg_ctr', (4 * BINS, 1), 'mul'))
 
 
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
-
-
-def measure(sides, iters, reps):
-    """{side: (median, min, max) us}; every side warmed, the order reversed every other repetition."""
+def timed_row(sides, iters, reps):
+    """(stat, its row with fused_wins).  Every callable is warmed once and each side's first once
+    more; the order of the sides is reversed every other repetition."""
     for fns in sides.values():
         for f in fns:
             f()
         fns[0]()
     torch.cuda.synchronize()
-    t = {k: [] for k in sides}
-    for r in range(reps):
-        for k in (list(sides) if r % 2 == 0 else list(sides)[::-1]):
-            t[k].append(time_calls(sides[k], iters))
-    return {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
-
-
-def report(stat, fused='fused', modules='modules'):
-    res = {}
-    for k, (med, lo, hi) in stat.items():
-        res[k + '_us'] = round(med, 1)
-        res[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
-    res['fused_wins'] = bool(stat[fused][2] < stat[modules][1])
-    return res
+    stat = measure(sides, iters, reps, warmup=0, reverse=True)
+    return stat, dict(put_times({}, stat, 1), fused_wins=wins(stat, 'fused', 'modules'))
 
 
 def shares(res, nbytes, flops, us):
@@ -83,18 +55,13 @@ def shares(res, nbytes, flops, us):
                fused_share_of_f32_mfma_peak=round(flops / PEAK_FLOPS * 1e6 / us, 3))
 
 
-def max_rel_diff(ref, got):
-    return max(float((a - b).abs().max() / a.abs().max()) for a, b in zip(ref, got))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--reps', type=int, default=9)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'head_convs', 'bench_head_convs.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_head_convs needs a HIP device')
+    require_gpu('bench_head_convs')
     from frcnn_amd import ops
     from frcnn_amd.heads.fcos_head import FCOSHead
     from frcnn_amd.heads.retina_head import RetinaHead
@@ -115,8 +82,7 @@ def main():
         tower = conv_of(CIN)
         sides = {'modules': [lambda i=i: [torch.relu_(tower(x)) for x in xs[i]] for i in range(SETS)],
                  'fused': [lambda i=i: ops.conv3x3_bias_act_levels(tower, xs[i], relu=True) for i in range(SETS)]}
-        stat = measure(sides, args.iters, args.reps)
-        r = report(stat)
+        stat, r = timed_row(sides, args.iters, args.reps)
         r['max_rel_diff_vs_modules'] = max_rel_diff(sides['modules'][0](), sides['fused'][0]())
         shares(r, 4.0 * (2 * pixels * CIN + 9 * CIN * CIN), 2.0 * pixels * 9 * CIN * CIN, stat['fused'][0])
         res['tower'] = r
@@ -147,10 +113,9 @@ def main():
             sides = {'modules': [lambda i=i: modules(i) for i in range(SETS)],
                      'fused': [lambda i=i, convs=convs, kw=kw: ops.conv3x3_out_levels(convs, xs[i], **kw)
                                for i in range(SETS)]}
-            stat = measure(sides, args.iters, args.reps)
-            r = report(stat)
+            stat, r = timed_row(sides, args.iters, args.reps)
             ref, got = sides['modules'][0](), sides['fused'][0]()
-            r['max_rel_diff_vs_modules'] = max_rel_diff([t for g in ref for t in g], [t for g in got for t in g])
+            r['max_rel_diff_vs_modules'] = max_rel_diff(ref, got)
             c = sum(widths)
             shares(r, 4.0 * (pixels * (CIN + c) + 9 * CIN * c), 2.0 * pixels * 9 * CIN * c, stat['fused'][0])
             r['class'] = ['out', CIN, widths[0], widths[1] if len(widths) > 1 else 0]
@@ -187,17 +152,14 @@ def main():
             sides = {'modules': [lambda i=i: forward(head, i, shipped, False) for i in range(SETS)],
                      'fused': [lambda i=i: forward(head, i, shipped) for i in range(SETS)],
                      'fused_every_part': [lambda i=i: forward(head, i, frozenset()) for i in range(SETS)]}
-            stat = measure(sides, args.iters, args.reps)
-            r = report(stat)
+            stat, r = timed_row(sides, args.iters, args.reps)
             ref, got = sides['modules'][0](), sides['fused'][0]()
-            r['max_rel_diff_vs_modules'] = max_rel_diff([t for g in ref for t in g], [t for g in got for t in g])
+            r['max_rel_diff_vs_modules'] = max_rel_diff(ref, got)
             res['forward'][name] = r
             print(name, json.dumps(r), flush=True)
             del head
     ops._HEAD_CONVS_EXCLUDED = shipped
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

@@ -19,15 +19,11 @@ that time."""
 import argparse
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import REPO, compare, require_gpu, write_json
 
 SIZES = [(152, 256), (76, 128), (38, 64), (19, 32), (10, 16)]
 B, C, REFINE = 2, 256, 2
@@ -55,36 +51,12 @@ def torch_bfp(feats, r=REFINE):
     return outs
 
 
-def time_calls(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters  # us per call
-
-
-def compare(a, b, iters, reps=5):
-    """us per call of a and b, alternating: (median a, median b, all a, all b)."""
-    for _ in range(5):
-        a()
-        b()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for _ in range(reps):
-        ta.append(time_calls(a, iters))
-        tb.append(time_calls(b, iters))
-    return float(np.median(ta)), float(np.median(tb)), [round(v, 2) for v in ta], [round(v, 2) for v in tb]
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'libra', 'bench_libra.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_libra needs a HIP device')
+    require_gpu('bench_libra')
     from frcnn_amd import ops
     from frcnn_amd.necks import BFP
     from frcnn_amd.region import IoUBalancedNegSampler
@@ -109,7 +81,7 @@ def main():
     def fwd_torch():
         with torch.no_grad():
             torch_bfp(feats)
-    th, tt, ah, at = compare(fwd_hip, fwd_torch, args.iters)
+    th, tt, ah, at = compare(fwd_hip, fwd_torch, args.iters, args.iters, warmup=5)
     fb = 2 * level_bytes
     res['bfp_forward'] = {'hip_us': round(th, 2), 'torch_us': round(tt, 2), 'hip_runs_us': ah, 'torch_runs_us': at,
                           'algorithmic_bytes': fb, 'hip_GBps': round(fb / th / 1e3, 1),
@@ -125,7 +97,8 @@ def main():
             outs = fn(gin + [gin[3][:, :, ::2, ::2]])
             torch.autograd.backward(outs, gouts)
         return run
-    th, tt, ah, at = compare(with_view(bfp), with_view(torch_bfp), max(args.iters // 2, 10))
+    half = max(args.iters // 2, 10)
+    th, tt, ah, at = compare(with_view(bfp), with_view(torch_bfp), half, half, warmup=5)
     fbb = 4 * level_bytes
     res['bfp_forward_backward'] = {'hip_us': round(th, 2), 'torch_us': round(tt, 2), 'hip_runs_us': ah,
                                    'torch_runs_us': at, 'algorithmic_bytes': fbb,
@@ -150,14 +123,12 @@ def main():
 
     def random_sampler():
         ops.sample_labels(lab, num, n, max_num, pos_num, lists=True)
-    ti, tr, ai, ar = compare(iou_sampler, random_sampler, args.iters * 2)
+    ti, tr, ai, ar = compare(iou_sampler, random_sampler, args.iters * 2, args.iters * 2, warmup=5)
     ops.set_sampler_mode('numpy')
     res['sampler'] = {'rows_per_image': n, 'images': S, 'max_num': max_num, 'pos_num': pos_num, 'num_bins': 3,
                       'iou_balanced_us': round(ti, 2), 'random_us': round(tr, 2), 'iou_balanced_runs_us': ai,
                       'random_runs_us': ar, 'note': 'host call to host call, output allocations included'}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

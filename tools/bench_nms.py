@@ -10,14 +10,13 @@ same for the RPN's one-launch NMS (nms_fused_kernel, the product's path inside
 frh_rpn_proposals): µs per call, and per block of segment 0 when its column's last tile was
 flagged, when the loader started / saw the column complete / published, when it was resolved."""
 import argparse
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, 'tools'), REPO, os.path.join(REPO, 'pytorch-faster-rcnn_amd')]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
+from benchlib import on_path, time_calls
+
+on_path()
 import bench  # noqa: E402
 from frcnn_amd import ops, _lib, set_sampler_mode  # noqa: E402
 import toolslib  # noqa: E402
@@ -55,16 +54,8 @@ def main():
         assert s == 0, lib.frh_last_error()
 
     for fn, name in ((plain, 'product'), (stamped, 'stamped')):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        print('{}: {:.2f} us per call (mask + scan)'.format(name, e0.elapsed_time(e1) / args.iters * 1e3), flush=True)
+        print('{}: {:.2f} us per call (mask + scan)'.format(name, time_calls(fn, args.iters, sleep=False, warmup=3)),
+              flush=True)
     ref_keep, ref_kc = keep.clone(), kc.clone()
     plain()
     torch.cuda.synchronize()
@@ -99,17 +90,8 @@ def main():
                                       _lib.ptr(stm), _lib.stream_of(rows))
         assert r == 0, lib.frh_last_error()
     for fn, name in ((fused, 'one-launch'), (lambda: fused(fst), 'one-launch stamped')):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        print('{}: {:.2f} us per call (flag memset + kernel)'.format(name, e0.elapsed_time(e1) / args.iters * 1e3),
-              flush=True)
+        print('{}: {:.2f} us per call (flag memset + kernel)'.format(
+            name, time_calls(fn, args.iters, sleep=False, warmup=3)), flush=True)
         assert torch.equal(kc, ref_kc) and all(torch.equal(keep[s, :int(kc[s])], ref_keep[s, :int(kc[s])])
                                                for s in range(S))
     fs = fst.cpu().numpy()

@@ -9,14 +9,13 @@ bit-identical to the product kernel (variant 0).  Variant 1 (stamped product bui
 prints the per-wave phase timeline.  --calib: known-byte launches for FETCH_SIZE
 calibration (run under rocprofv3 --pmc FETCH_SIZE)."""
 import argparse
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, 'tools'), REPO, os.path.join(REPO, 'pytorch-faster-rcnn_amd')]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
+from benchlib import on_path, time_calls
+
+on_path()
 import bench  # noqa: E402
 from frcnn_amd import ops, _lib, set_sampler_mode  # noqa: E402
 import toolslib  # noqa: E402
@@ -158,45 +157,27 @@ def main():
                                               shapes[0][0], C, _lib.ptr(rois), _lib.ptr(levels), K, ph, pw, sr, 0,
                                               _lib.ptr(full), _lib.ptr(wsp), wsb, _lib.stream_of(out))
             assert s == 0, lib.frh_last_error()
-        for _ in range(3):
-            launch()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            launch()
-        e1.record()
-        torch.cuda.synchronize()
-        warm = e0.elapsed_time(e1) / args.iters * 1e3
-        cold = None
-        if args.cold:
+        warm = time_calls(launch, args.iters, sleep=False, warmup=3)
+
+        def after(disturb):
+            """us per launch when `disturb` runs before each one: an arm of disturb + launch minus an arm
+            of disturb alone.  Inline because the two interleave inside one event pair."""
             arms = []
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             for with_launch in (True, False):
                 torch.cuda.synchronize()
                 e0.record()
                 for _ in range(args.iters):
-                    torch.sum(scratch, dim=0, out=sink)
+                    disturb()
                     if with_launch:
                         launch()
                 e1.record()
                 torch.cuda.synchronize()
                 arms.append(e0.elapsed_time(e1) * 1e3)
-            cold = (arms[0] - arms[1]) / args.iters
-        aw = None
+            return (arms[0] - arms[1]) / args.iters
+        cold = after(lambda: torch.sum(scratch, dim=0, out=sink)) if args.cold else None
         if args.after_write:  # does the Infinity Cache keep lines the trunk has just written?
-            arms = []
-            for with_launch in (True, False):
-                torch.cuda.synchronize()
-                e0.record()
-                for _ in range(args.iters):
-                    for f in fv:
-                        f.mul_(1.0)
-                    if with_launch:
-                        launch()
-                e1.record()
-                torch.cuda.synchronize()
-                arms.append(e0.elapsed_time(e1) * 1e3)
-            aw = (arms[0] - arms[1]) / args.iters
+            aw = after(lambda: [f.mul_(1.0) for f in fv])
             print('variant {:>3}: after a rewrite of the features {:7.2f} us'.format(v, aw), flush=True)
         summary.setdefault(v, []).append((warm, cold))
         if v in STAMPED:

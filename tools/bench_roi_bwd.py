@@ -10,16 +10,12 @@ Algorithmic bytes: 4*C*sum_K*49 gradient read + 2*4*C*sum H_l*W_
 accumulate once per cell)."""
 import argparse
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, 'tools'), os.path.join(REPO, 'pytorch-faster-rcnn_amd')]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import torch
 
-from frcnn_amd import ops, _lib  # noqa: E402
-from bench_roi_sets import load_set  # noqa: E402
+from benchlib import time_calls
+from frcnn_amd import ops, _lib
+from bench_roi_sets import load_set
 
 
 def main():
@@ -81,16 +77,7 @@ def main():
         outs = {}
         for nm, fn in fns:
             outs[nm] = fn()
-            for _ in range(2):
-                fn()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            res[nm] = e0.elapsed_time(e1) * 1e3 / args.iters
+            res[nm] = time_calls(fn, args.iters, sleep=False, warmup=2)
         perm = torch.randperm(K, device=dev, generator=torch.Generator(device=dev).manual_seed(4))
         a, b = fixed(), fixed(rois[perm].contiguous(), levels[perm].contiguous(), g[perm].contiguous())
         at = atomic()

@@ -19,31 +19,14 @@ f32-matrix peak (a whole-call rate: both launches)."""
 import argparse
 import json
 import os
-import sys
 
-import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, 'pytorch-faster-rcnn_amd'))
+from benchlib import PEAK_FLOPS, REPO, max_rel_diff, measure, put_times, require_gpu, wins, write_json
 
 CIN = COUT = 256
 ROIS = (512, 1000, 2000)
-PEAK_FLOPS = 157.3e12
 SETS = 3
-
-
-def time_calls(fns, iters):
-    """us per call of fns[i % len(fns)], queued behind a sleep so the host runs ahead."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(100000000)
-    e0.record()
-    for i in range(iters):
-        fns[i % len(fns)]()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def main():
@@ -52,8 +35,7 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'roi_conv', 'bench_roi_conv.json'))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_roi_conv needs a HIP device')
+    require_gpu('bench_roi_conv')
     from frcnn_amd import _lib, ops
     torch.backends.cudnn.benchmark = True
     dev = torch.device('cuda', 0)
@@ -78,39 +60,25 @@ def main():
                      p(bn.running_var), float(bn.eps), r, CIN, COUT, 1, p(ws), _lib.stream_of(xs[i]))
                 return lambda: _lib.call('frh_roi_conv3x3_bn_act', *a)
             sides = {'parent': [parent(i) for i in range(SETS)], 'fused': [entry(i) for i in range(SETS)]}
-            for fns in sides.values():
-                for f in fns:
-                    f()
-                    f()
-            torch.cuda.synchronize()
+            stat = measure(sides, args.iters, args.reps, warmup=2)
             ref = sides['parent'][0]()
             sides['fused'][0]()
-            maxdiff = float((ref - ys[0]).abs().max() / ref.abs().max())
-            t = {k: [] for k in sides}
-            for _ in range(args.reps):
-                for k, fns in sides.items():
-                    t[k].append(time_calls(fns, args.iters))
-            stat = {k: (float(np.median(v)), float(min(v)), float(max(v))) for k, v in t.items()}
+            maxdiff = max_rel_diff(ref, ys[0])
             flops = 2.0 * r * 49 * 9 * CIN * COUT
             row = {'r': r, 'cin': CIN, 'cout': COUT, 'gflop': round(flops / 1e9, 2),
                    'fused_in_ops': bool(ops.roi_conv3x3_fused_ok(conv, bn, xs[0])),
                    'max_rel_diff_vs_parent': maxdiff}
-            for k, (med, lo, hi) in stat.items():
-                row[k + '_us'] = round(med, 1)
-                row[k + '_us_min_max'] = [round(lo, 1), round(hi, 1)]
-            row['fused_wins'] = stat['fused'][2] < stat['parent'][1]
+            put_times(row, stat, 1)['fused_wins'] = wins(stat, 'fused', 'parent')
             row['fused_TFLOPs'] = round(flops / stat['fused'][0] / 1e6, 1)
             row['fused_share_of_f32_matrix_peak'] = round(flops / stat['fused'][0] / 1e6 / (PEAK_FLOPS / 1e12), 3)
             rows.append(row)
             print('r {:5d}  parent {:8.1f} us [{:.1f}, {:.1f}]  fused {:8.1f} us [{:.1f}, {:.1f}]  {:.1f} TFLOP/s '
-                  '({:.0%} of peak)  wins {}'.format(r, *stat['parent'], *stat['fused'], row['fused_TFLOPs'],
+                  '({:.0%} of peak)  wins {}'.format(r, *stat['parent'][:3], *stat['fused'][:3], row['fused_TFLOPs'],
                                                      row['fused_share_of_f32_matrix_peak'], row['fused_wins']),
                   flush=True)
             del xs, ys
     res = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'reps': args.reps, 'shapes': rows}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'w') as f:
-        json.dump(res, f, indent=1)
+    write_json(args.out, res)
     print(json.dumps(res))
 
 

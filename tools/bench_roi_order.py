@@ -5,16 +5,13 @@ outputs land in the permuted order (this measures scheduling only).
 
     python tools/bench_roi_order.py [--sets bench,voc,train] [--iters 20] [--rounds 3]"""
 import argparse
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, 'tools'), os.path.join(REPO, 'pytorch-faster-rcnn_amd')]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from frcnn_amd import ops, _lib  # noqa: E402
-from bench_roi_sets import load_set, tap_cells  # noqa: E402
+from benchlib import time_calls
+from frcnn_amd import ops, _lib
+from bench_roi_sets import load_set, tap_cells
 
 
 def main():
@@ -59,16 +56,7 @@ def main():
                 def f():
                     _lib.call('frh_roi_align_fwd_strided', len(feats), fp, hw, st, sc, shapes[0][0], C, _lib.ptr(r),
                               _lib.ptr(lv), K, 7, 7, 2, 0, _lib.ptr(out), _lib.stream_of(out))
-                for _ in range(3):
-                    f()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                for _ in range(args.iters):
-                    f()
-                e1.record()
-                torch.cuda.synchronize()
-                res[k].append(e0.elapsed_time(e1) * 1e3 / args.iters)
+                res[k].append(time_calls(f, args.iters, sleep=False, warmup=3))
         print('set {}: '.format(name) + ', '.join('{} {:.2f} us'.format(k, float(np.median(v))) for k, v in res.items()),
               flush=True)
 

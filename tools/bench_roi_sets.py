@@ -14,15 +14,12 @@ import argparse
 import ctypes
 import json
 import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, 'tools'), REPO, os.path.join(REPO, 'pytorch-faster-rcnn_amd'),
-                os.path.join(REPO, 'tests', 'golden')]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from frcnn_amd import ops, _lib  # noqa: E402
+from benchlib import PEAK_BYTES, REPO, time_calls
+from frcnn_amd import ops, _lib
 
 SETS = {'bench': 'cfg2_rois.npz', 'voc': 'cfg2_rois_voc.npz', 'train': 'cfg2_rois_train.npz'}
 STAMPED = {9, 68, 94}  # tools variants writing per-item phase stamps (s_memrealtime): quad, band, channel-group
@@ -164,16 +161,7 @@ def main():
         times = {k: [] for k in kinds}
         for _ in range(args.rounds):
             for k in kinds:
-                for _ in range(3):
-                    fns[k]()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                e0.record()
-                for _ in range(args.iters):
-                    fns[k]()
-                e1.record()
-                torch.cuda.synchronize()
-                times[k].append(e0.elapsed_time(e1) * 1e3 / args.iters)
+                times[k].append(time_calls(fns[k], args.iters, sleep=False, warmup=3))
         print('set {}: K {} levels {} tap cells p50 {:.0f} p90 {:.0f} >512 {:.1%}; algorithmic {:.1f} MB'.format(
             name, K, np.bincount(levels.cpu().numpy(), minlength=4).tolist(), np.median(cells),
             np.percentile(cells, 90), (cells > 512).mean(), nbytes / 1e6), flush=True)
@@ -182,7 +170,7 @@ def main():
         for k in kinds:
             us = float(np.median(times[k]))
             same = bool(torch.equal(outs[k], outs['product']))
-            frac = nbytes / (us * 1e-6) / 8e12
+            frac = nbytes / (us * 1e-6) / PEAK_BYTES
             summary[name]['kernels'][k] = {'us': us, 'frac': frac, 'bit_identical_to_product': same}
             print('  {:8s} {:8.2f} us  frac {:.3f}  bit-identical to product: {}'.format(k, us, frac, same), flush=True)
             if k in stamps and int(k[1:]) in STAMPED_CG:

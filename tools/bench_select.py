@@ -15,16 +15,13 @@ synthetic labels, the same three measurements.
 """
 import argparse
 import json
-import os
-import sys
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, REPO)
-sys.path.insert(0, HERE)
+from benchlib import on_path, time_calls
+
+on_path()
 
 RPN_PHASES = ['start', 'keys+hist flushed', 'barrier 1 passed', 'bucket 1 found', 'hist 2 flushed',
               'barrier 2 passed', 'plan', 'slots reserved', 'selections decoded', 'barrier 3 passed',
@@ -49,17 +46,8 @@ def timeline(stm, names):
     return out
 
 
-def time_calls(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
+def us_of_call(fn, iters):
+    return time_calls(fn, iters, sleep=False, warmup=3)
 
 
 def main():
@@ -84,11 +72,11 @@ def main():
     anchors = head._flat_anchors(grids, dev)
     argv = (cls, reg, anchors, head.num_anchors, 1, [0.0] * 4, [1.0] * 4, [(600.0, 1000.0)] * 2, [0.0] * 2,
             2000, 2000, 2000, 0.7)
-    one = time_calls(lambda: ops.rpn_proposals(*argv), args.iters)
-    four = time_calls(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_launches, 'launches')),
+    one = us_of_call(lambda: ops.rpn_proposals(*argv), args.iters)
+    four = us_of_call(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_launches, 'launches')),
                       args.iters)
-    nms2 = time_calls(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_nms2, 'nms2')), args.iters)
-    mlaunch = time_calls(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_merge_launch, 'merge_launch')),
+    nms2 = us_of_call(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_nms2, 'nms2')), args.iters)
+    mlaunch = us_of_call(lambda: ops.rpn_proposals(*argv, _entry=(lib.frh_rpn_proposals_merge_launch, 'merge_launch')),
                          args.iters)
     gx = max(max((3 * h * w + 4095) // 4096, (2000 + 63) // 64) for h, w in grids)
     stm = torch.zeros(2 * len(grids), gx, 16, dtype=torch.int64, device=dev)
@@ -135,8 +123,8 @@ def main():
                            .astype(np.int64)).to(dev)
     num = torch.tensor([n] * S, dtype=torch.int32, device=dev)
     ops.set_sampler_mode('device', seed=5)
-    one = time_calls(lambda: ops.sample_labels(lab, num, n, 256, 128, mode='device', lists=True), args.iters)
-    two = time_calls(lambda: ops.sample_labels(lab, num, n, 256, 128, mode='device', lists=True,
+    one = us_of_call(lambda: ops.sample_labels(lab, num, n, 256, 128, mode='device', lists=True), args.iters)
+    two = us_of_call(lambda: ops.sample_labels(lab, num, n, 256, 128, mode='device', lists=True,
                                                _entry=(lib.frh_sample_random_launches, 'launches')), args.iters)
     sst = torch.zeros(S, (n + 4095) // 4096, 16, dtype=torch.int64, device=dev)
 

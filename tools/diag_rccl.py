@@ -15,6 +15,8 @@ import socket
 import torch
 import torch.distributed as dist
 
+from benchlib import time_calls
+
 
 def main():
     dev = torch.device('cuda', 0)
@@ -49,13 +51,7 @@ def main():
     ok['broadcast'] = bool(torch.equal(t, x))
     torch.cuda.synchronize()
     # timing of the bucket-sized all-reduce over the one rank (the per-bucket floor of DDP's exchange)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        dist.all_reduce(t, op=dist.ReduceOp.AVG)
-    e1.record()
-    torch.cuda.synchronize()
-    out['avg_allreduce_25MB_us'] = e0.elapsed_time(e1) * 1e3 / 20
+    out['avg_allreduce_25MB_us'] = time_calls(lambda: dist.all_reduce(t, op=dist.ReduceOp.AVG), 20, sleep=False)
     out['ok'] = ok
     dist.destroy_process_group()
     print(json.dumps(out), flush=True)

@@ -13,13 +13,12 @@ and an NHWC pass move the same bytes).
 import argparse
 import collections
 import json
-import os
-import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
+from benchlib import on_path, time_calls
+
+on_path()
 
 
 def main():
@@ -52,15 +51,7 @@ def main():
             backbones.bn_act = nhwc_bn_act
             x = imgs.contiguous(memory_format=torch.channels_last)
         with torch.no_grad():
-            for _ in range(3):
-                model.neck(model.backbone(x))
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                model.neck(model.backbone(x))
-            e1.record()
-            torch.cuda.synchronize()
+            event_us = time_calls(lambda: model.neck(model.backbone(x)), args.iters, sleep=False, warmup=3)
             with profile(activities=[ProfilerActivity.CUDA]) as prof:
                 for _ in range(args.iters):
                     model.neck(model.backbone(x))
@@ -76,7 +67,7 @@ def main():
                 c = 'miopen_aux'
             cat[c] += e.time_range.elapsed_us() / args.iters
             top[n[:80]] += e.time_range.elapsed_us() / args.iters
-        res[layout] = {'us_per_forward_event': round(e0.elapsed_time(e1) * 1e3 / args.iters, 1),
+        res[layout] = {'us_per_forward_event': round(event_us, 1),
                        'kernel_us_by_category': {k: round(v, 1) for k, v in cat.items()},
                        'top_kernels': {k: round(v, 1) for k, v in sorted(top.items(), key=lambda kv: -kv[1])[:25]}}
         print(layout, json.dumps(res[layout]['kernel_us_by_category']), res[layout]['us_per_forward_event'],

@@ -6,29 +6,18 @@ the lateral sums), the P6 subsample, and the RPN head (3x3 conv + ReLU, 1x1 cls 
 convs on P2..P6) -- NCHW as today vs NHWC (channels_last weights and inputs; the inputs'
 conversion is NOT timed: a fused transpose-add in the top-down pass would produce them).
 Also times the plain NCHW -> NHWC copy of P2..P5 (what a separate transpose would cost)."""
-import os
-import sys
+import argparse
 
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'pytorch-faster-rcnn_amd'))
+from benchlib import time_calls
 
-
-def timeit(fn, iters=20):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3  # us
+PROTOCOL = dict(iters=20, sleep=False, warmup=3)
 
 
 def main():
+    argparse.ArgumentParser(description=__doc__.split('\n')[0]).parse_args()
     torch.backends.cudnn.benchmark = True
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
@@ -47,13 +36,14 @@ def main():
             return outs, [cls(h) for h in hid], [reg(h) for h in hid]
 
     res = {}
-    res['nchw_fpn_rpn_us'] = timeit(lambda: trunk(lat))
+    res['nchw_fpn_rpn_us'] = time_calls(lambda: trunk(lat), **PROTOCOL)
     with torch.no_grad():
-        res['nchw_to_nhwc_copy_P2_P5_us'] = timeit(lambda: [x.contiguous(memory_format=torch.channels_last) for x in lat])
+        res['nchw_to_nhwc_copy_P2_P5_us'] = time_calls(
+            lambda: [x.contiguous(memory_format=torch.channels_last) for x in lat], **PROTOCOL)
     for m in fpn + [rpn, cls, reg]:
         m.to(memory_format=torch.channels_last)
     lat_cl = [x.contiguous(memory_format=torch.channels_last) for x in lat]
-    res['nhwc_fpn_rpn_us'] = timeit(lambda: trunk(lat_cl))
+    res['nhwc_fpn_rpn_us'] = time_calls(lambda: trunk(lat_cl), **PROTOCOL)
     outs, c, r = trunk(lat_cl)
     res['nhwc_P2_strides'] = list(outs[0].stride())
     res['nhwc_cls_strides'] = list(c[0].stride())
