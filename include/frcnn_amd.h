@@ -765,6 +765,41 @@ int32_t frh_deform_conv3x3_act_levels(int32_t num_levels, const void* const* xs,
                                       const int64_t* level_strides, const int64_t* offset_strides, int32_t relu,
                                       void* stream);
 
+/* The backward of frh_deform_conv3x3_act for one level, with that entry's definition, layouts
+ * and sample-point arithmetic.  gy = dL/dy and y (the forward's output; NULL: the forward ran
+ * without ReLU, otherwise gy counts only where y > 0) are contiguous NHWC [n, h, wd, cout].  With
+ * S[n, c, k, p] the blended sample of input channel c, tap k at position p and
+ * G[n, c, k, p] = sum_co w[co, c, k] gy[n, co, p]:
+ *   gx   (NULL: skipped) contiguous NHWC [n, h, wd, cin], ACCUMULATED into -- the caller zeroes
+ *        it: every G adds G (hy hx, hy lx, ly hx, ly lx) to its four neighbours;
+ *   goff (NULL: skipped) [n, 18 dg, h, wd] contiguous, always the full offset map, also in the
+ *        guided mode (the gradients of the shape map and of offset_w are two contractions of
+ *        it): goff[n, g 18 + 2 k, p] = sum_{c in g} G (hx (v10 - v00) + lx (v11 - v01)), channel
+ *        + 1 = sum_{c in g} G (hy (v01 - v00) + ly (v11 - v10)); floor has derivative 0, so at an
+ *        integer coordinate this is the one-sided derivative;
+ *   gw   (NULL: skipped) [cout, cin, 3, 3] = sum_{n, p} gy[n, co, p] S[n, c, k, p].
+ * Neighbours outside the map count as 0 and receive nothing; where the forward's float range
+ * test fails (a non-finite or huge offset included) no address is formed and the sample
+ * contributes exact zeros to gx, goff and gw.  offset_w != NULL (guided): the offsets are
+ * re-formed in registers exactly as the forward does, and goff is bit for bit that of the
+ * explicit mode on that map.
+ * Launches: the weight repack and the data launch (G on the f32 MFMA from a gy tile held in
+ * LDS; gx with no-return float atomics, so its last bits depend on arrival order; goff summed
+ * over a group's channels in a fixed order and stored once) when gx or goff is wanted; the
+ * weight launch (per-position-split partial slabs in the workspace) and a reduce in split order
+ * when gw is.  goff and gw are bit-identical from launch to launch.  workspace:
+ * frh_deform_conv3x3_bwd_workspace(n, cin, cout, h, wd) bytes.
+ * Checks as the forward's: cin % 16 == 0, (cin / dg) % 4 == 0, cout % 64 == 0, every pointer but
+ * offset and goff 16-byte aligned, no output or workspace overlapping an input or another
+ * output (anything else: FRH_EINVAL); 2^31 positions or more, or cout > 256 (the gy tile is 64 x
+ * cout floats of LDS): FRH_EUNSUPPORTED; n == 0, or no output wanted, launches nothing. */
+size_t frh_deform_conv3x3_bwd_workspace(int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd);
+int32_t frh_deform_conv3x3_bwd(const float* x, const float* offset, const float* offset_w, const float* w,
+                               const float* y, const float* gy, float* gx, float* goff, float* gw,
+                               float* workspace, int64_t n, int32_t cin, int32_t cout, int32_t dg, int32_t h,
+                               int32_t wd, int64_t sn, int64_t sy, int64_t sx, const int64_t* offset_strides,
+                               void* stream);
+
 /* FPN top-down merge into channels-last levels (lib/necks.py:72-84):
  * out[b, y, x, c] = (lat[b, c, y, x] + bias[c]) + up[b, iy, ix, c] with torch's nearest rule
  * (iy = min(floor(y * (float)up_h / height), up_h - 1); y / 2 when height == 2 * up_h);

@@ -127,6 +127,9 @@ SIGNATURES = {
                                        c_i64, c_i64, c_i64, P(c_i64), c_i32, c_vp]),
     'frh_deform_conv3x3_act_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), c_vp, c_vp, P(c_vp), c_vp, c_i64, c_i32, c_i32,
                                               c_i32, P(c_i32), P(c_i64), P(c_i64), c_i32, c_vp]),
+    'frh_deform_conv3x3_bwd_workspace': (c_size, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    'frh_deform_conv3x3_bwd': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
+                                       c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, P(c_i64), c_vp]),
     'frh_ga_targets': (c_i32, [c_i32, c_i32, P(c_i32), P(c_f32), c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32,
                                c_f32, c_vp, c_vp, c_vp, c_vp]),
     'frh_bn_act_maxpool': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_i32, c_vp]),

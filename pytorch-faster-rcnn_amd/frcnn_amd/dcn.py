@@ -2,9 +2,12 @@
 mmdet.ops.dcn (lib/heads/guided_head.py:3,95), for the one form the reference uses: kernel 3,
 stride 1, padding 1, dilation 1, no bias, `deformable_groups` offset groups.
 
-Inference runs the fused HIP kernel (ops.deform_conv3x3: frh_deform_conv3x3_act); wherever a
-gradient is needed the module takes ops.deform_conv3x3_torch, the gather + matmul restatement
-autograd differentiates.  There is no backward kernel."""
+Inference runs the fused HIP kernel (ops.deform_conv3x3: frh_deform_conv3x3_act).  Wherever a
+gradient is needed the module by default takes ops.deform_conv3x3_torch, the gather + matmul
+restatement autograd differentiates; with the class attribute `hip_grad = True` it keeps the HIP
+forward and runs frh_deform_conv3x3_bwd (csrc/deform_conv3x3_bwd.hip) as its backward wherever
+ops.deform_conv3x3 allows it (HIP f32 tensors, accepted shapes, no deterministic backward asked
+for)."""
 import math
 
 import torch
@@ -14,6 +17,8 @@ from . import ops
 
 
 class DeformConv(nn.Module):
+    hip_grad = False  # True: training runs on the HIP forward and backward entries
+
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
                  deformable_groups=1, bias=False):
         super().__init__()
@@ -36,7 +41,7 @@ class DeformConv(nn.Module):
             self.weight.uniform_(-stdv, stdv)
 
     def forward(self, x, offset, relu=False):
-        return ops.deform_conv3x3(x, offset, self.weight, self.deformable_groups, relu)
+        return ops.deform_conv3x3(x, offset, self.weight, self.deformable_groups, relu, hip_grad=self.hip_grad)
 
     def extra_repr(self):
         return '{}, {}, kernel_size=3, padding=1, deformable_groups={}, bias=False'.format(

@@ -10,8 +10,10 @@ implements its text with four repairs ("GA-RPN deviations"):
 
 What runs where.  The adaption layer (offset_layer + DeformConv + ReLU) of all levels is one
 fused HIP launch pair where nothing needs a gradient (ops.deform_conv3x3_levels, guided mode:
-the 18 dg-channel offset map is never written), the torch restatement otherwise (training: there
-is no backward kernel).  The location and shape targets of the whole batch are one launch
+the 18 dg-channel offset map is never written).  Training by default takes the torch restatement;
+with the class attribute GuidedAnchor.hip_grad = True it is that one forward call
+(frh_deform_conv3x3_act_levels) and one frh_deform_conv3x3_bwd call per level in the backward.
+The location and shape targets of the whole batch are one launch
 (ops.ga_targets) instead of the reference's per-gt painting loops; the location loss runs over
 the un-compacted logits with -1 labels, which the focal-loss kernel skips.  GuidedAnchor.loss
 still meets the host twice a batch: targets() reads the smallest gt coordinate back (its
@@ -32,6 +34,8 @@ from ..utils import ChannelsLastConvs, init_module_normal, multi_apply, unpack_m
 
 
 class GuidedAnchor(ChannelsLastConvs):
+    hip_grad = False  # True: the adaption layer trains on the HIP forward and backward entries
+
     def __init__(self, in_channels=256, out_channels=256, anchor_scales=None, anchor_ratios=None, anchor_strides=None,
                  anchoring_means=(0.0, 0.0, 0.0, 0.0), anchoring_stds=(0.07, 0.07, 0.14, 0.14), deformable_groups=4,
                  sigma=8, loc_filter_thr=0.01, loss_loc=None, loss_shape=None):
@@ -109,10 +113,11 @@ class GuidedAnchor(ChannelsLastConvs):
         loc_outs = [self.loc_layer(f) for f in feats]
         shape_outs = [self.shape_layer(f) for f in feats]
         # relu(adapt_layer(feat, offset_layer(shape.detach()))) of every level: one fused launch pair
-        # where nothing needs a gradient, the torch restatement otherwise
+        # where nothing needs a gradient; otherwise the torch restatement, or with hip_grad the same
+        # forward with the HIP backward
         adapt_feats = ops.deform_conv3x3_levels(feats, [so.detach() for so in shape_outs], self.adapt_layer.weight,
                                                 self.deformable_groups, relu=True,
-                                                offset_weight=self.offset_layer.weight)
+                                                offset_weight=self.offset_layer.weight, hip_grad=self.hip_grad)
         return loc_outs, shape_outs, adapt_feats
 
     # ------------------------------------------------------------ targets and loss

@@ -1810,6 +1810,11 @@ def _dc_x_ok(x, cin):
 def deform_conv3x3_fused_ok(x, offset, weight, dg, offset_weight=None):
     """Whether deform_conv3x3 / deform_conv3x3_levels take the HIP entry for these arguments
     (offset_weight given: `offset` is the 2-channel shape map of the guided mode)."""
+    return _dc_shapes_ok(x, offset, weight, dg, offset_weight) and not _needs_grad(x, offset, weight, offset_weight)
+
+
+def _dc_shapes_ok(x, offset, weight, dg, offset_weight=None):
+    """deform_conv3x3_fused_ok without the gradient test: what the HIP entries accept."""
     if not (torch.is_tensor(weight) and weight.dim() == 4 and weight.is_cuda and weight.dtype == torch.float32
             and weight.is_contiguous() and weight.shape[2:] == (3, 3)):
         return False
@@ -1823,7 +1828,7 @@ def deform_conv3x3_fused_ok(x, offset, weight, dg, offset_weight=None):
     if offset_weight is not None and not (offset_weight.is_cuda and offset_weight.dtype == torch.float32
                                           and offset_weight.is_contiguous() and offset_weight.numel() == 36 * dg):
         return False
-    return _aligned16(x, weight, offset_weight) and not _needs_grad(x, offset, weight, offset_weight)
+    return _aligned16(x, weight, offset_weight)
 
 
 def _dc_ws(cin, cout, dev):
@@ -1835,20 +1840,8 @@ def _as_channels_last(x):
     return x if x.stride(1) == 1 else x.contiguous(memory_format=torch.channels_last)
 
 
-def deform_conv3x3(x, offset, weight, dg, relu=False, offset_weight=None):
-    """act(DeformConv(x, offset)) for a 3x3 / stride-1 / padding-1 deformable convolution without
-    bias: the HIP entry (frh_deform_conv3x3_act; the result is channels-last) when the tensors
-    are f32 on the HIP device, meet its shape conditions and nothing needs a gradient;
-    otherwise deform_conv3x3_torch, which autograd differentiates (training).  With
-    offset_weight [18 dg, 2(, 1, 1)] (guided mode) `offset` is the 2-channel shape map and the
-    offsets are the bias-free 1x1 convolution of it, formed inside the kernel."""
-    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
-    if x.is_cuda and x.dim() == 4:
-        x = _as_channels_last(x)
-    if not deform_conv3x3_fused_ok(x, offset, weight, dg, ow):
-        if ow is not None:
-            offset = nn.functional.conv2d(offset, ow.view(18 * dg, 2, 1, 1))
-        return deform_conv3x3_torch(x, offset, weight, dg, relu)
+def _dc_act(x, offset, weight, dg, relu, ow):
+    """One frh_deform_conv3x3_act call (arguments already checked)."""
     n, cin, h, w = x.shape
     cout = weight.shape[0]
     sn, _, sy, sx = x.stride()
@@ -1858,18 +1851,8 @@ def deform_conv3x3(x, offset, weight, dg, relu=False, offset_weight=None):
     return y
 
 
-def deform_conv3x3_levels(xs, offsets, weight, dg, relu=False, offset_weight=None):
-    """deform_conv3x3 with one shared weight on every level of a pyramid (at most 8): one repack
-    launch and one convolution launch (frh_deform_conv3x3_act_levels) when every level can take
-    the HIP entry; the per-level calls otherwise.  Same bits as the per-level calls."""
-    xs, offsets = list(xs), list(offsets)
-    if len(xs) != len(offsets):
-        raise AssertionError('deform_conv3x3_levels: one offset (or shape) map per level')
-    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
-    xs = [_as_channels_last(x) if x.is_cuda and x.dim() == 4 else x for x in xs]
-    if not (1 <= len(xs) <= 8 and all(deform_conv3x3_fused_ok(x, o, weight, dg, ow) for x, o in zip(xs, offsets))
-            and len({(x.shape[0], x.device) for x in xs}) == 1):
-        return [deform_conv3x3(x, o, weight, dg, relu, offset_weight) for x, o in zip(xs, offsets)]
+def _dc_act_levels(xs, offsets, weight, dg, relu, ow):
+    """One frh_deform_conv3x3_act_levels call (arguments already checked)."""
     n, dev = xs[0].shape[0], xs[0].device
     cout, cin = weight.shape[:2]
     ys = [_nhwc_empty((n, cout, x.shape[2], x.shape[3]), dev) for x in xs]
@@ -1877,6 +1860,139 @@ def deform_conv3x3_levels(xs, offsets, weight, dg, relu=False, offset_weight=Non
          ptr_array(ys), ptr(_dc_ws(cin, cout, dev)), n, cin, cout, int(dg), *_level_geometry(xs),
          i64_array([v for o in offsets for v in o.stride()]), int(bool(relu)), stream_of(xs[0]))
     return ys
+
+
+# Level shapes (cin, cout, n, h, w) on which a single-level hip_grad=True call still takes the
+# restatement: those where forward + backward on the HIP entries measured slower than the
+# restatement's (tools/bench_deform_conv_bwd.py, profiles/ga_rpn_bwd/bench_deform_conv_bwd.json;
+# us per forward + backward, median [min, max], HIP against restatement).  A lone small level pays
+# the latency floor of the forward (K is not split) and of the data launch by itself.  A pyramid
+# call is measured as one unit (17 651 [17 610, 17 697] against 49 787 [49 739, 49 900]) and is
+# not subject to this table.
+_DEFORM_BWD_EXCLUDED = {
+    (256, 256, 2, 19, 32),  # 1622.6 [1619.6, 1622.8] against 1088.5 [1086.8, 1091.5]
+    (256, 256, 2, 10, 16),  # 1543.7 [1543.5, 1544.9] against  656.6 [ 655.0,  657.6]
+}
+_DC_BWD_MAX_COUT = 256  # frh_deform_conv3x3_bwd: FRH_EUNSUPPORTED above
+
+
+def _dc_hip_grad_ok(xs, offsets, weight, dg, ow):
+    """Whether hip_grad=True runs these levels on the HIP forward with frh_deform_conv3x3_bwd as
+    its backward: something needs a gradient, the entries accept every level, and the backward
+    need not be deterministic (gx is summed with float atomics; the restatement is the
+    deterministic form)."""
+    if deterministic_backward() or not (1 <= len(xs) <= 8):
+        return False
+    if not all(_dc_shapes_ok(x, o, weight, dg, ow) for x, o in zip(xs, offsets)):
+        return False
+    cout, cin = weight.shape[:2]
+    if cout > _DC_BWD_MAX_COUT or len({(x.shape[0], x.device) for x in xs}) != 1:
+        return False
+    if len(xs) == 1 and (cin, cout, xs[0].shape[0], xs[0].shape[2], xs[0].shape[3]) in _DEFORM_BWD_EXCLUDED:
+        return False
+    return _needs_grad(weight, ow, *xs, *offsets)
+
+
+class _DeformConv3x3(torch.autograd.Function):
+    """act(DeformConv) of one or more levels sharing a weight: the HIP forward (one
+    frh_deform_conv3x3_act / _act_levels call) with frh_deform_conv3x3_bwd, one call per level,
+    as its backward.  Inputs: dg, relu, weight, ow ([18 dg, 2] or None), the levels' x, then
+    their offset (ow None) or shape maps."""
+
+    @staticmethod
+    def forward(ctx, dg, relu, weight, ow, *maps):
+        L = len(maps) // 2
+        xs, offs = list(maps[:L]), list(maps[L:])
+        if L == 1:
+            ys = [_dc_act(xs[0], offs[0], weight, dg, relu, ow)]
+        else:
+            ys = _dc_act_levels(xs, offs, weight, dg, relu, ow)
+        ctx.dg, ctx.relu, ctx.levels, ctx.guided = int(dg), bool(relu), L, ow is not None
+        ctx.save_for_backward(weight, ow, *xs, *offs, *(ys if relu else []))
+        return tuple(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gys):
+        L, dg, guided = ctx.levels, ctx.dg, ctx.guided
+        weight, ow = ctx.saved_tensors[:2]
+        xs, offs = ctx.saved_tensors[2:2 + L], ctx.saved_tensors[2 + L:2 + 2 * L]
+        ys = ctx.saved_tensors[2 + 2 * L:] if ctx.relu else [None] * L
+        need = ctx.needs_input_grad
+        cout, cin = weight.shape[:2]
+        g_w = g_ow = None
+        g_xs, g_offs = [None] * L, [None] * L
+        for i in range(L):  # the levels' gw are added in level order
+            if gys[i] is None:
+                continue
+            x, off = xs[i], offs[i]
+            n, _, h, w = x.shape
+            dev = x.device
+            want_off = need[4 + L + i] or (guided and need[3])
+            gy = gys[i].float().contiguous(memory_format=torch.channels_last)
+            gx = torch.zeros(n, h, w, cin, dtype=torch.float32, device=dev).permute(0, 3, 1, 2) if need[4 + i] else None
+            goff = torch.empty(n, 18 * dg, h, w, dtype=torch.float32, device=dev) if want_off else None
+            gw = torch.empty_like(weight) if need[2] else None
+            ws = workspace(_lib.query('frh_deform_conv3x3_bwd_workspace', n, cin, cout, h, w), dev)
+            sn, _, sy, sx = x.stride()
+            call('frh_deform_conv3x3_bwd', ptr(x), ptr(off), ptr(ow), ptr(weight), ptr(ys[i]), ptr(gy), ptr(gx),
+                 ptr(goff), ptr(gw), ptr(ws), n, cin, cout, dg, h, w, sn, sy, sx, i64_array(off.stride()), stream_of(x))
+            g_xs[i] = gx
+            if gw is not None:
+                g_w = gw if g_w is None else g_w + gw
+            if goff is None:
+                continue
+            if not guided:
+                g_offs[i] = goff
+                continue
+            if need[3]:  # the offset layer is a 1x1 conv without bias: two contractions of goff
+                t = torch.einsum('nchw,njhw->cj', goff, off)
+                g_ow = t if g_ow is None else g_ow + t
+            if need[4 + L + i]:
+                g_offs[i] = torch.einsum('cj,nchw->njhw', ow, goff)
+        return (None, None, g_w, g_ow, *g_xs, *g_offs)
+
+
+def deform_conv3x3(x, offset, weight, dg, relu=False, offset_weight=None, hip_grad=False):
+    """act(DeformConv(x, offset)) for a 3x3 / stride-1 / padding-1 deformable convolution without
+    bias: the HIP entry (frh_deform_conv3x3_act; the result is channels-last) when the tensors
+    are f32 on the HIP device, meet its shape conditions and nothing needs a gradient;
+    otherwise deform_conv3x3_torch, which autograd differentiates (training).  With
+    offset_weight [18 dg, 2(, 1, 1)] (guided mode) `offset` is the 2-channel shape map and the
+    offsets are the bias-free 1x1 convolution of it, formed inside the kernel.
+    hip_grad=True: where a gradient is needed and the entries accept the tensors, the forward is
+    the HIP entry all the same and its backward frh_deform_conv3x3_bwd (gx by float atomics; no
+    double backward).  CPU tensors, refused shapes, shapes in _DEFORM_BWD_EXCLUDED and a
+    deterministic backward (deterministic_backward()) keep the restatement."""
+    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
+    if x.is_cuda and x.dim() == 4:
+        x = _as_channels_last(x)
+    if hip_grad and _dc_hip_grad_ok([x], [offset], weight, dg, ow):
+        return _DeformConv3x3.apply(dg, relu, weight, ow, x, offset)[0]
+    if not deform_conv3x3_fused_ok(x, offset, weight, dg, ow):
+        if ow is not None:
+            offset = nn.functional.conv2d(offset, ow.view(18 * dg, 2, 1, 1))
+        return deform_conv3x3_torch(x, offset, weight, dg, relu)
+    return _dc_act(x, offset, weight, dg, relu, ow)
+
+
+def deform_conv3x3_levels(xs, offsets, weight, dg, relu=False, offset_weight=None, hip_grad=False):
+    """deform_conv3x3 with one shared weight on every level of a pyramid (at most 8): one repack
+    launch and one convolution launch (frh_deform_conv3x3_act_levels) when every level can take
+    the HIP entry; the per-level calls otherwise.  Same bits as the per-level calls.
+    hip_grad=True, where every level qualifies (deform_conv3x3): that one forward call, and one
+    frh_deform_conv3x3_bwd call per level as its backward."""
+    xs, offsets = list(xs), list(offsets)
+    if len(xs) != len(offsets):
+        raise AssertionError('deform_conv3x3_levels: one offset (or shape) map per level')
+    ow = None if offset_weight is None else offset_weight.reshape(18 * dg, 2)
+    xs = [_as_channels_last(x) if x.is_cuda and x.dim() == 4 else x for x in xs]
+    if hip_grad and _dc_hip_grad_ok(xs, offsets, weight, dg, ow):
+        return list(_DeformConv3x3.apply(dg, relu, weight, ow, *xs, *offsets))
+    if not (1 <= len(xs) <= 8 and all(deform_conv3x3_fused_ok(x, o, weight, dg, ow) for x, o in zip(xs, offsets))
+            and len({(x.shape[0], x.device) for x in xs}) == 1):
+        return [deform_conv3x3(x, o, weight, dg, relu, offset_weight, hip_grad) for x, o in zip(xs, offsets)]
+    return _dc_act_levels(xs, offsets, weight, dg, relu, ow)
 
 
 def ga_targets(grid_sizes, strides, gt_list, level_list, img_shapes, center_ratio, ignore_ratio, shape_center_ratio):
