@@ -23,7 +23,7 @@
 // with label >= 0 (focal_elem, the element frh_cls_loss_fwd kind 0 sums), and at the positives
 // giou_loss of (-p_l, -p_t, p_r, p_b) against the normalised target times the centerness target,
 // and the centerness BCE.  The workgroups' partials are finalised in a fixed order by the last
-// one to arrive (fan_in4, loss_common.h); no float atomics.  The backward recomputes and writes
+// one to arrive (fan_in, loss_common.h); no float atomics.  The backward recomputes and writes
 // every gradient element exactly once.
 //
 // Numerics: f32 in the reference's operation order; the assignment is bit-exact, the loss sums
@@ -177,8 +177,11 @@ __global__ void __launch_bounds__(kLossThreads) fcos_loss_fwd_kernel(FcosLossArg
   __syncthreads();
   const float pt = block_sum_f(acc_ctr, scratch);
   const int np = block_sum_i(npos, iscratch);
+  const int g = gridDim.x;
+  const float p[4] = {pc, pb, pt, (float)np};  // the count is exact in f32: a workgroup counts fewer than 2^24
+  const int nb[4] = {g, g, g, g};
   double res[4];
-  if (!fan_in4(pc, pb, pt, np, counter, partial, res)) return;
+  if (!fan_in(p, nb, counter, partial, res)) return;
   if (threadIdx.x == 0) {
     // the modules' (sum * loss_weight) / num_pos in f32; max(num_pos, 1) where the reference divides by 0
     const float n = (float)res[3];
@@ -247,12 +250,6 @@ int32_t make_fcos_loss(FcosLossArgs* a, const float* cls, int64_t c, int64_t sk,
   return FRH_OK;
 }
 
-int fcos_loss_grid(int64_t m) {
-  int64_t b = (m + kLossThreads - 1) / kLossThreads;
-  if (b < 1) b = 1;
-  return (int)(b < kMaxPartials ? b : kMaxPartials);
-}
-
 }  // namespace
 }  // namespace frh
 
@@ -298,16 +295,16 @@ int32_t frh_fcos_loss_fwd(const float* cls, int64_t c, int64_t cls_sk, int64_t c
                           float alpha, float gamma, float cls_weight, float bbox_weight, float ctr_weight,
                           const int32_t* status, float* out, void* workspace, size_t ws_bytes, void* stream) {
   FcosLossArgs a;
-  const int32_t st = make_fcos_loss(&a, cls, c, cls_sk, cls_si, reg, reg_ss, reg_si, ctr, ctr_si, label, ltrb, ctr_t,
-                                    m, reg_mean, reg_std, alpha, gamma);
+  int32_t st = make_fcos_loss(&a, cls, c, cls_sk, cls_si, reg, reg_ss, reg_si, ctr, ctr_si, label, ltrb, ctr_t, m,
+                              reg_mean, reg_std, alpha, gamma);
   if (st != FRH_OK) return st;
   FRH_REQUIRE(out, "fcos loss: null output");
-  FRH_REQUIRE(workspace && ws_bytes >= kCounterBytes + kLossPartialArrays * kMaxPartials * sizeof(float),
-              "fcos loss: workspace too small");
-  char* w = static_cast<char*>(workspace);
+  LossWorkspace ws;
+  st = split_workspace(workspace, ws_bytes, "fcos loss", &ws);
+  if (st != FRH_OK) return st;
   const FcosScale o{cls_weight, bbox_weight, ctr_weight};
-  hipLaunchKernelGGL(fcos_loss_fwd_kernel, dim3(fcos_loss_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o,
-                     reinterpret_cast<uint32_t*>(w), reinterpret_cast<float*>(w + kCounterBytes), out, status);
+  hipLaunchKernelGGL(fcos_loss_fwd_kernel, dim3(loss_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o,
+                     ws.counter, ws.partial, out, status);
   return check_launch("frh_fcos_loss_fwd");
 }
 

@@ -26,7 +26,7 @@
 // launch less on a path that is launch-bound at the head's size (44 k positions, 3.5 MB of
 // class logits).  The per-lane sums are reduced per workgroup and the workgroups' partials are
 // finalised in a fixed order by the last workgroup to arrive (the arrival-counter fan-in of
-// losses.hip: det_fan_in), so a call is deterministic; no float atomics.
+// loss_common.h: fan_in), so a call is deterministic; no float atomics.
 //
 // The backward has the same two phases and recomputes q and w (constants of the gradient, as
 // the reference detaches them): phase 1 writes the 4*bins regression gradients of a positive
@@ -150,12 +150,15 @@ __device__ __forceinline__ PosEval eval_positive(const GflArgs& a, int64_t j, in
   return r;
 }
 
-// The last workgroup to arrive sums the four partial arrays in a fixed order (losses.hip:
-// det_fan_in) and scales as the reference's modules do: (sum * loss_weight) / avg_factor in f32.
+// The last workgroup to arrive sums the four partial arrays in a fixed order (loss_common.h:
+// fan_in) and scales as the reference's modules do: (sum * loss_weight) / avg_factor in f32.
 __device__ void gfl_fan_in(float pc, float pd, float pb, int np, uint32_t* counter, float* partial,
                            const GflScale& o, float* out, const int32_t* status) {
+  const int g = gridDim.x;
+  const float p[4] = {pc, pd, pb, (float)np};  // the count is exact in f32: a workgroup counts fewer than 2^24
+  const int nb[4] = {g, g, g, g};
   double res[4];
-  if (!fan_in4(pc, pd, pb, np, counter, partial, res)) return;  // loss_common.h
+  if (!fan_in(p, nb, counter, partial, res)) return;
   if (threadIdx.x == 0) {
     const float npos = (float)res[3];
     const float d = fmaxf(npos, 1.0f);
@@ -352,12 +355,6 @@ int32_t make_gfl(GflArgs* a, const float* cls, int64_t c, int64_t sk, int64_t si
   return FRH_OK;
 }
 
-int gfl_grid(int64_t m) {
-  int64_t b = (m + kLossThreads - 1) / kLossThreads;
-  if (b < 1) b = 1;
-  return (int)(b < kMaxPartials ? b : kMaxPartials);
-}
-
 }  // namespace
 }  // namespace frh
 
@@ -376,12 +373,12 @@ int32_t frh_gfl_loss_fwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cl
   if (st != FRH_OK) return st;
   FRH_REQUIRE(out, "gfl loss: null output");
   FRH_REQUIRE(dfl_avg_factor != 0.0f, "gfl loss: dfl_avg_factor must be nonzero");
-  FRH_REQUIRE(workspace && ws_bytes >= kCounterBytes + kLossPartialArrays * kMaxPartials * sizeof(float),
-              "gfl loss: workspace too small");
-  char* w = static_cast<char*>(workspace);
+  LossWorkspace ws;
+  st = split_workspace(workspace, ws_bytes, "gfl loss", &ws);
+  if (st != FRH_OK) return st;
   const GflScale o{cls_weight, dfl_weight, bbox_weight, dfl_avg_factor};
-  hipLaunchKernelGGL(gfl_loss_fwd_kernel, dim3(gfl_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o,
-                     reinterpret_cast<uint32_t*>(w), reinterpret_cast<float*>(w + kCounterBytes), out, status);
+  hipLaunchKernelGGL(gfl_loss_fwd_kernel, dim3(loss_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o,
+                     ws.counter, ws.partial, out, status);
   return check_launch("frh_gfl_loss_fwd");
 }
 
@@ -399,7 +396,7 @@ int32_t frh_gfl_loss_bwd(const float* cls, int64_t c, int64_t cls_sk, int64_t cl
   FRH_REQUIRE(g && fwd_out && (m == 0 || (grad_cls && grad_reg)), "gfl loss bwd: null gradient");
   if (m == 0) return FRH_OK;
   const GflScale o{cls_weight, dfl_weight, bbox_weight, dfl_avg_factor};
-  hipLaunchKernelGGL(gfl_loss_bwd_kernel, dim3(gfl_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o, g,
+  hipLaunchKernelGGL(gfl_loss_bwd_kernel, dim3(loss_grid(m)), dim3(kLossThreads), 0, as_stream(stream), a, o, g,
                      fwd_out, grad_cls, gc_sk, gc_si, grad_reg, gr_sc, gr_si);
   return check_launch("frh_gfl_loss_bwd");
 }

@@ -1,7 +1,7 @@
 // Pieces the fused loss files share (losses.hip, gfl.hip, fcos.hip): the launch shape, the
-// workspace layout behind frh_loss_workspace(), torch's BCE-with-logits / sigmoid forms, the
-// focal element, the block sums, the four-sum arrival fan-in and the status-word read.  Moved
-// here from losses.hip and gfl.hip unchanged.
+// workspace layout behind frh_loss_workspace() with its size check and split, torch's
+// BCE-with-logits / sigmoid forms, the focal element, the block sums, the arrival-counter fan-in
+// and the status-word read.
 #pragma once
 #include "common.h"
 
@@ -56,34 +56,36 @@ __device__ __forceinline__ float focal_elem(float x, float t, float alpha, float
   return bce * w;
 }
 
-// The arrival-counter fan-in of a forward with three sums and a positive count (from gfl.hip's
-// gfl_fan_in, shared with fcos.hip).  Thread 0 holds the workgroup's partials; every workgroup
-// stores them write-through, drains and adds to the counter; the workgroup whose add returns
-// gridDim.x - 1 gets true (in all its threads) and, in res, the four sums over the workgroups in
-// a fixed order (double: one slot per thread, then a tree).  Its thread 0 writes the outputs and
-// then resets the counter.  partial: kLossPartialArrays arrays of kMaxPartials floats.
-__device__ inline bool fan_in4(float p0, float p1, float p2, int np, uint32_t* counter, float* partial,
-                               double (&res)[4]) {
+// The arrival-counter fan-in of every fused forward, over N sums (MI355X_MICROARCH.md hand-off
+// table, row 1: one signalling lane per workgroup, one unsharded counter, the last adder told by
+// its add's return value).  Thread 0 holds the workgroup's partials p; every workgroup stores
+// them write-through into slot blockIdx.x of its N arrays, drains and adds to the counter.  The
+// workgroup whose add returns gridDim.x - 1 gets true (in all its threads) and, in res, sum q
+// over the first nb[q] workgroups in a fixed order (double: one slot per thread, then a tree), so
+// a call is deterministic.  Its thread 0 writes the outputs and then resets the counter.
+// partial: kLossPartialArrays arrays of kMaxPartials floats, array q at q * kMaxPartials.
+template <int N>
+__device__ inline bool fan_in(const float (&p)[N], const int (&nb)[N], uint32_t* counter, float* partial,
+                              double (&res)[N]) {
+  static_assert(N <= kLossPartialArrays, "the workspace holds kLossPartialArrays partial arrays");
   __shared__ double s[kLossThreads];
   __shared__ int last;
   if (threadIdx.x == 0) {
-    __hip_atomic_store(partial + blockIdx.x, p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + kMaxPartials + blockIdx.x, p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + 2 * kMaxPartials + blockIdx.x, p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + 3 * kMaxPartials + blockIdx.x, (float)np, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);  // exact in f32: a workgroup counts fewer than 2^24
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+      __hip_atomic_store(partial + q * kMaxPartials + blockIdx.x, p[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint32_t old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = old == gridDim.x - 1;
   }
   __syncthreads();
-  if (!last) return false;
+  if (!last) return false;  // workgroup-uniform: the barriers below are reached by all threads or none
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float* p = partial + q * kMaxPartials;
+  for (int q = 0; q < N; ++q) {
+    const float* a = partial + q * kMaxPartials;
     double v = 0.0;
-    for (int j = threadIdx.x; j < (int)gridDim.x; j += kLossThreads)
-      v += (double)__hip_atomic_load(const_cast<float*>(p + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int j = threadIdx.x; j < nb[q]; j += kLossThreads)
+      v += (double)__hip_atomic_load(const_cast<float*>(a + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s[threadIdx.x] = v;
     __syncthreads();
     for (int w = kLossThreads / 2; w > 0; w >>= 1) {
@@ -113,6 +115,29 @@ __device__ __forceinline__ int block_sum_i(int v, int* scratch) {
 // undefined, and the step's own loss read carries the failure without an extra host sync.
 __device__ __forceinline__ bool status_set(const int32_t* status) {
   return status && __hip_atomic_load(const_cast<int32_t*>(status), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
+// Host side.  The forward grid: one workgroup per kLossThreads items, at least one, capped at the
+// partial slots.
+inline int loss_grid(int64_t work) {
+  int64_t b = (work + kLossThreads - 1) / kLossThreads;
+  if (b < 1) b = 1;
+  return (int)(b < kMaxPartials ? b : kMaxPartials);
+}
+
+constexpr size_t kLossWorkspaceBytes = kCounterBytes + kLossPartialArrays * kMaxPartials * sizeof(float);
+
+struct LossWorkspace {
+  uint32_t* counter;  // zero between calls
+  float* partial;
+};
+
+// the caller's workspace, checked and split; `what` names the loss in the message
+inline int32_t split_workspace(void* workspace, size_t ws_bytes, const char* what, LossWorkspace* ws) {
+  FRH_REQUIRE(workspace && ws_bytes >= kLossWorkspaceBytes, "%s: workspace too small", what);
+  char* w = static_cast<char*>(workspace);
+  *ws = LossWorkspace{reinterpret_cast<uint32_t*>(w), reinterpret_cast<float*>(w + kCounterBytes)};
+  return FRH_OK;
 }
 
 }  // namespace frh

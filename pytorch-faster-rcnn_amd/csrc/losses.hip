@@ -20,13 +20,13 @@
 // element's derivative and writes g * dL/dx, reading the upstream gradient
 // from device memory (no host sync).
 //
-// The forward's finalisation rides in the same launch: every workgroup stores
-// its partial write-through (agent-scope relaxed store), drains, and adds to an
-// arrival counter; the workgroup whose add returns nb - 1 sums the nb partials
-// (agent-scope loads) in the fixed order of the former separate finalise
-// launch and resets the counter (MI355X_MICROARCH.md hand-off table, row 1:
-// one signalling lane per workgroup, one unsharded counter, last adder told by
-// its add's return value; grids capped at 256 workgroups).
+// The forward's finalisation rides in the same launch: the arrival-counter
+// fan-in of loss_common.h (fan_in) over one sum, or over two for the one-launch
+// head loss; the last workgroup to arrive writes the loss and resets the
+// counter (grids capped at 256 workgroups).  Each loss family has one
+// accumulation loop (cls_accumulate, l1_accumulate) that its own kernel and
+// the head-loss kernel both call, so the two sum the same elements in the same
+// order by construction.
 //
 // Bytes per element: forward 4 (logit) + 8/C (label); backward 4 + 4 + 8/C.
 // Numerics follow torch's formulas (binary_cross_entropy_with_logits via
@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace frh {
 namespace {
@@ -85,49 +86,32 @@ __device__ __forceinline__ float elem_target(const ClsArgs& a, int64_t i, int64_
   return label_at(a, i) == k + 1 ? 1.0f : 0.0f;
 }
 
+// where a one-sum forward leaves its loss
 struct FanIn {
-  uint32_t* counter;      // zero between calls
-  float* partial;         // [gridDim.x]
+  LossWorkspace ws;
   float* out;
   const int32_t* status;  // nullable: the caller's device status word; nonzero -> NaN loss
 };
 
-// Thread 0 holds the workgroup's partial sum.  The last workgroup to arrive sums
-// all partials in a fixed order (double accumulation: one slot per thread, then
-// a tree) and writes the loss.
-__device__ void fan_in_finalize(float block_total, const FanIn& f) {
-  __shared__ double s[kLossThreads];
-  __shared__ int last;
+// Thread 0 holds the workgroup's partial sum; the last workgroup to arrive writes the loss.
+__device__ __forceinline__ void finalize_one(float block_total, const FanIn& f) {
+  const float p[1] = {block_total};
+  const int nb[1] = {(int)gridDim.x};
+  double res[1];
+  if (!fan_in(p, nb, f.ws.counter, f.ws.partial, res)) return;
   if (threadIdx.x == 0) {
-    __hip_atomic_store(f.partial + blockIdx.x, block_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t old = __hip_atomic_fetch_add(f.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = old == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  double v = 0.0;
-  for (int j = threadIdx.x; j < (int)gridDim.x; j += kLossThreads)
-    v += (double)__hip_atomic_load(f.partial + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  s[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kLossThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    f.out[0] = status_set(f.status) ? NAN : (float)s[0];
-    __hip_atomic_store(f.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    f.out[0] = status_set(f.status) ? NAN : (float)res[0];
+    __hip_atomic_store(f.ws.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
+// This thread's share of the classification sum as workgroup b of nb: the softmax kind strides
+// over rows, the sigmoid kinds over elements.
 template <int kKind>
-__global__ void __launch_bounds__(kLossThreads) cls_loss_fwd_kernel(ClsArgs a, FanIn f) {
-  __shared__ float scratch[kLossThreads / kWave];
+__device__ __forceinline__ float cls_accumulate(const ClsArgs& a, int b, int nb) {
   float acc = 0.0f;
   if constexpr (kKind == kSoftmaxCe) {
-    for (int64_t i = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; i < a.n;
-         i += (int64_t)gridDim.x * kLossThreads) {
+    for (int64_t i = b * (int64_t)kLossThreads + threadIdx.x; i < a.n; i += (int64_t)nb * kLossThreads) {
       if (ignored(a, i)) continue;
       const float* row = a.x + i * a.sr;
       float m = -INFINITY;
@@ -140,8 +124,7 @@ __global__ void __launch_bounds__(kLossThreads) cls_loss_fwd_kernel(ClsArgs a, F
     }
   } else {
     const int64_t total = a.n * a.c;
-    for (int64_t e = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; e < total;
-         e += (int64_t)gridDim.x * kLossThreads) {
+    for (int64_t e = b * (int64_t)kLossThreads + threadIdx.x; e < total; e += (int64_t)nb * kLossThreads) {
       int64_t i, k;
       elem_index(a, e, &i, &k);
       if (ignored(a, i)) continue;
@@ -150,7 +133,13 @@ __global__ void __launch_bounds__(kLossThreads) cls_loss_fwd_kernel(ClsArgs a, F
       acc += kKind == kFocal ? focal_elem(x, t, a.alpha, a.gamma, nullptr) : bce_logits(x, t);
     }
   }
-  fan_in_finalize(block_sum_f(acc, scratch), f);
+  return acc;
+}
+
+template <int kKind>
+__global__ void __launch_bounds__(kLossThreads) cls_loss_fwd_kernel(ClsArgs a, FanIn f) {
+  __shared__ float scratch[kLossThreads / kWave];
+  finalize_one(block_sum_f(cls_accumulate<kKind>(a, blockIdx.x, gridDim.x), scratch), f);
 }
 
 template <int kKind>
@@ -242,13 +231,12 @@ struct BalancedL1Elem {
   }
 };
 
+// this thread's share of the regression sum as workgroup b of nb
 template <class Elem>
-__global__ void __launch_bounds__(kLossThreads) l1_fwd_kernel(L1Args a, Elem el, FanIn f) {
-  __shared__ float scratch[kLossThreads / kWave];
+__device__ __forceinline__ float l1_accumulate(const L1Args& a, const Elem& el, int b, int nb) {
   float acc = 0.0f;
   const int64_t total = a.n * a.m;
-  for (int64_t e = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * kLossThreads) {
+  for (int64_t e = b * (int64_t)kLossThreads + threadIdx.x; e < total; e += (int64_t)nb * kLossThreads) {
     int64_t i = e / a.m, j = e - i * a.m, off;
     if (!l1_row(a, i, &off)) continue;
     if (a.xs_l && (a.label[i] >= a.n_sel)) {
@@ -258,7 +246,13 @@ __global__ void __launch_bounds__(kLossThreads) l1_fwd_kernel(L1Args a, Elem el,
     float d = fabsf(a.x[off + j * a.xs_j] - a.y[i * a.ys_i + j * a.ys_j]);
     acc += el.value(d);
   }
-  fan_in_finalize(block_sum_f(acc, scratch), f);
+  return acc;
+}
+
+template <class Elem>
+__global__ void __launch_bounds__(kLossThreads) l1_fwd_kernel(L1Args a, Elem el, FanIn f) {
+  __shared__ float scratch[kLossThreads / kWave];
+  finalize_one(block_sum_f(l1_accumulate(a, el, blockIdx.x, gridDim.x), scratch), f);
 }
 
 // gx must be zero-filled by the caller: only the selected, unmasked elements are written.
@@ -285,9 +279,9 @@ __global__ void __launch_bounds__(kLossThreads) l1_bwd_kernel(L1Args a, Elem el,
 // calc_loss with a sampler: anchor_head.py:113-139, bbox_head.py:56-87).  Workgroup b
 // takes the cls elements of workgroup b of cls_loss_fwd_kernel's grid (b < nbc) and the
 // smooth-L1 elements of workgroup b of l1_fwd_kernel<SmoothL1Elem>'s grid (b < nbr); the last
-// workgroup to arrive sums each loss's partials in the fixed order of fan_in_finalize,
-// so both sums equal the separate launches' bit for bit, and applies the heads' scaling
-// as torch does it: loss = (sum * loss_weight) / avg_factor in f32.
+// workgroup to arrive sums each loss's nbc / nbr partials in fan_in's fixed order, so both
+// sums equal the separate launches' bit for bit, and applies the heads' scaling as torch
+// does it: loss = (sum * loss_weight) / avg_factor in f32.
 struct DetScale {
   float wc, dc, wr, dr;
   float* out;             // [2]: cls, reg
@@ -295,37 +289,21 @@ struct DetScale {
   const int32_t* status;  // nullable: device status word; nonzero -> NaN losses
 };
 
-__device__ void det_fan_in(float pc, float pr, uint32_t* counter, float* partial, int nbc, int nbr,
-                           const DetScale& o) {
-  __shared__ double s[kLossThreads];
-  __shared__ int last;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(partial + blockIdx.x, pc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + kMaxPartials + blockIdx.x, pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = old == gridDim.x - 1;
-  }
+template <int kKind>
+__global__ void __launch_bounds__(kLossThreads) det_loss_fwd_kernel(ClsArgs a, int nbc, L1Args r, int nbr,
+                                                                    LossWorkspace ws, DetScale o) {
+  __shared__ float scratch[kLossThreads / kWave];
+  const int b = blockIdx.x;
+  const float acc = b < nbc ? cls_accumulate<kKind>(a, b, nbc) : 0.0f;
+  const float accr = b < nbr ? l1_accumulate(r, SmoothL1Elem{r.beta}, b, nbr) : 0.0f;
+  const float pc = block_sum_f(acc, scratch);
   __syncthreads();
-  if (!last) return;
-  float res[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int nb = q ? nbr : nbc;
-    const float* p = partial + q * kMaxPartials;
-    double v = 0.0;
-    for (int j = threadIdx.x; j < nb; j += kLossThreads)
-      v += (double)__hip_atomic_load(const_cast<float*>(p + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-      __syncthreads();
-    }
-    res[q] = (float)s[0];
-    __syncthreads();
-  }
+  const float p[2] = {pc, block_sum_f(accr, scratch)};
+  const int nb[2] = {nbc, nbr};
+  double sum[2];
+  if (!fan_in(p, nb, ws.counter, ws.partial, sum)) return;
   if (threadIdx.x == 0) {
+    const float res[2] = {(float)sum[0], (float)sum[1]};
     if (o.ndev) {
       const int32_t nd = *o.ndev;
       const float d = (float)nd;
@@ -336,67 +314,23 @@ __device__ void det_fan_in(float pc, float pr, uint32_t* counter, float* partial
       o.out[1] = (res[1] * o.wr) / o.dr;
     }
     if (status_set(o.status)) o.out[0] = o.out[1] = NAN;
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ws.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
-template <int kKind>
-__global__ void __launch_bounds__(kLossThreads) det_loss_fwd_kernel(ClsArgs a, int nbc, L1Args r, int nbr,
-                                                                    uint32_t* counter, float* partial, DetScale o) {
-  __shared__ float scratch[kLossThreads / kWave];
-  float acc = 0.0f;
-  if ((int)blockIdx.x < nbc) {
-    if constexpr (kKind == kSoftmaxCe) {
-      for (int64_t i = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; i < a.n; i += (int64_t)nbc * kLossThreads) {
-        if (ignored(a, i)) continue;
-        const float* row = a.x + i * a.sr;
-        float m = -INFINITY;
-        for (int64_t k = 0; k < a.c; ++k) m = fmaxf(m, row[k * a.sc]);
-        float sm = 0.0f;
-        for (int64_t k = 0; k < a.c; ++k) sm += expf(row[k * a.sc] - m);
-        int64_t l = label_at(a, i);
-        float xl = (l >= 0 && l < a.c) ? row[l * a.sc] : NAN;
-        acc += (logf(sm) + m) - xl;
-      }
-    } else {
-      const int64_t total = a.n * a.c;
-      for (int64_t e = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; e < total;
-           e += (int64_t)nbc * kLossThreads) {
-        int64_t i, k;
-        elem_index(a, e, &i, &k);
-        if (ignored(a, i)) continue;
-        float x = a.x[i * a.sr + k * a.sc];
-        float t = elem_target(a, i, k);
-        acc += kKind == kFocal ? focal_elem(x, t, a.alpha, a.gamma, nullptr) : bce_logits(x, t);
-      }
-    }
-  }
-  float accr = 0.0f;
-  if ((int)blockIdx.x < nbr) {
-    const int64_t total = r.n * r.m;
-    for (int64_t e = blockIdx.x * (int64_t)kLossThreads + threadIdx.x; e < total; e += (int64_t)nbr * kLossThreads) {
-      int64_t i = e / r.m, j = e - i * r.m, off;
-      if (!l1_row(r, i, &off)) continue;
-      if (r.xs_l && (r.label[i] >= r.n_sel)) {
-        accr += NAN;
-        continue;
-      }
-      float d = fabsf(r.x[off + j * r.xs_j] - r.y[i * r.ys_i + j * r.ys_j]);
-      accr += d < r.beta ? (d * d) / (2.0f * r.beta) : d - 0.5f * r.beta;
-    }
-  }
-  const float pc = block_sum_f(acc, scratch);
-  __syncthreads();
-  const float pr = block_sum_f(accr, scratch);
-  det_fan_in(pc, pr, counter, partial, nbc, nbr, o);
+// f(std::integral_constant<int, kind>()) for a kind that check_cls has passed
+template <class F>
+void dispatch_kind(int32_t kind, F f) {
+  if (kind == kFocal)
+    f(std::integral_constant<int, kFocal>());
+  else if (kind == kSigmoidBce)
+    f(std::integral_constant<int, kSigmoidBce>());
+  else
+    f(std::integral_constant<int, kSoftmaxCe>());
 }
 
-
-int grid_for(int64_t work) {
-  int64_t b = (work + kLossThreads - 1) / kLossThreads;
-  if (b < 1) b = 1;
-  return (int)(b < kMaxPartials ? b : kMaxPartials);
-}
+// the grid of a classification forward or backward: softmax strides over rows
+int cls_grid(int32_t kind, const ClsArgs& a) { return loss_grid(kind == kSoftmaxCe ? a.n : a.n * a.c); }
 
 int32_t check_cls(int32_t kind, const ClsArgs& a) {
   FRH_REQUIRE(kind >= kFocal && kind <= kSoftmaxCe, "cls loss: unknown kind %d", kind);
@@ -451,7 +385,13 @@ L1Args make_l1(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const f
   return a;
 }
 
-int32_t make_balanced(float beta, float alpha, float gamma, BalancedL1Elem* el) {
+// The element of an entry's (beta, alpha, gamma): smooth L1 takes beta alone.
+int32_t make_elem(float beta, float, float, SmoothL1Elem* el) {
+  *el = SmoothL1Elem{beta};
+  return FRH_OK;
+}
+
+int32_t make_elem(float beta, float alpha, float gamma, BalancedL1Elem* el) {
   FRH_REQUIRE(alpha > 0.0f && gamma > 0.0f, "balanced l1: alpha and gamma must be > 0");
   const double b = exp((double)gamma / (double)alpha) - 1.0;
   *el = BalancedL1Elem{beta, alpha, gamma, (float)b, (float)((double)alpha / b), (float)((double)gamma / b),
@@ -459,21 +399,38 @@ int32_t make_balanced(float beta, float alpha, float gamma, BalancedL1Elem* el) 
   return FRH_OK;
 }
 
+// The bodies of frh_smooth_l1_* and frh_balanced_l1_*; `what` names the loss in a refusal, `entry`
+// the entry point in a launch error.
 template <class Elem>
-int32_t launch_l1_fwd(const L1Args& a, const Elem& el, const FanIn& f, void* stream, const char* what) {
-  hipLaunchKernelGGL(l1_fwd_kernel<Elem>, dim3(grid_for(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
-                     f);
-  return check_launch(what);
+int32_t l1_fwd(const L1Args& a, float alpha, float gamma, const int32_t* status, float* out, void* workspace,
+               size_t ws_bytes, void* stream, const char* what, const char* entry) {
+  int32_t st = check_l1(a);
+  if (st != FRH_OK) return st;
+  Elem el;
+  st = make_elem(a.beta, alpha, gamma, &el);
+  if (st != FRH_OK) return st;
+  FRH_REQUIRE(out, "%s: null output", what);
+  LossWorkspace ws;
+  st = split_workspace(workspace, ws_bytes, what, &ws);
+  if (st != FRH_OK) return st;
+  hipLaunchKernelGGL(l1_fwd_kernel<Elem>, dim3(loss_grid(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
+                     FanIn{ws, out, status});
+  return check_launch(entry);
 }
 
 template <class Elem>
-int32_t launch_l1_bwd(const L1Args& a, const Elem& el, const float* grad_out, float* grad_x, int64_t gs_i,
-                      int64_t gs_j, int64_t gs_l, void* stream, const char* what) {
+int32_t l1_bwd(const L1Args& a, float alpha, float gamma, const float* grad_out, float* grad_x, int64_t gs_i,
+               int64_t gs_j, int64_t gs_l, void* stream, const char* entry) {
+  int32_t st = check_l1(a);
+  if (st != FRH_OK) return st;
+  Elem el;
+  st = make_elem(a.beta, alpha, gamma, &el);
+  if (st != FRH_OK) return st;
   FRH_REQUIRE(grad_out && (a.n == 0 || grad_x), "l1 bwd: null gradient");
   if (a.n == 0) return FRH_OK;
-  hipLaunchKernelGGL(l1_bwd_kernel<Elem>, dim3(grid_for(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
+  hipLaunchKernelGGL(l1_bwd_kernel<Elem>, dim3(loss_grid(a.n * a.m)), dim3(kLossThreads), 0, as_stream(stream), a, el,
                      grad_out, grad_x, gs_i, gs_j, gs_l);
-  return check_launch(what);
+  return check_launch(entry);
 }
 
 }  // namespace
@@ -483,12 +440,7 @@ using namespace frh;
 
 extern "C" {
 
-size_t frh_loss_workspace(void) { return kCounterBytes + kLossPartialArrays * kMaxPartials * sizeof(float); }
-
-static FanIn fan_in(void* workspace, float* out, const int32_t* status) {
-  char* w = static_cast<char*>(workspace);
-  return FanIn{reinterpret_cast<uint32_t*>(w), reinterpret_cast<float*>(w + kCounterBytes), out, status};
-}
+size_t frh_loss_workspace(void) { return kLossWorkspaceBytes; }
 
 int32_t frh_cls_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int64_t sr, int64_t sc,
                          const void* target, int32_t target_is_float, float alpha, float gamma,
@@ -497,16 +449,14 @@ int32_t frh_cls_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int
   int32_t st = check_cls(kind, a);
   if (st != FRH_OK) return st;
   FRH_REQUIRE(out, "cls loss: null output");
-  FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "cls loss: workspace too small");
-  const FanIn f = fan_in(workspace, out, status);
-  int nb = grid_for(kind == kSoftmaxCe ? n : n * c);
-  hipStream_t s = as_stream(stream);
-  if (kind == kFocal)
-    hipLaunchKernelGGL(cls_loss_fwd_kernel<kFocal>, dim3(nb), dim3(kLossThreads), 0, s, a, f);
-  else if (kind == kSigmoidBce)
-    hipLaunchKernelGGL(cls_loss_fwd_kernel<kSigmoidBce>, dim3(nb), dim3(kLossThreads), 0, s, a, f);
-  else
-    hipLaunchKernelGGL(cls_loss_fwd_kernel<kSoftmaxCe>, dim3(nb), dim3(kLossThreads), 0, s, a, f);
+  LossWorkspace ws;
+  st = split_workspace(workspace, ws_bytes, "cls loss", &ws);
+  if (st != FRH_OK) return st;
+  const FanIn f{ws, out, status};
+  dispatch_kind(kind, [&](auto k) {
+    hipLaunchKernelGGL(cls_loss_fwd_kernel<k()>, dim3(cls_grid(kind, a)), dim3(kLossThreads), 0, as_stream(stream), a,
+                       f);
+  });
   return check_launch("frh_cls_loss_fwd");
 }
 
@@ -518,43 +468,26 @@ int32_t frh_cls_loss_bwd(int32_t kind, const float* x, int64_t n, int64_t c, int
   if (st != FRH_OK) return st;
   FRH_REQUIRE(grad_out && (n == 0 || grad_x), "cls loss bwd: null gradient");
   if (n == 0) return FRH_OK;
-  int nb = grid_for(kind == kSoftmaxCe ? n : n * c);
-  hipStream_t s = as_stream(stream);
-  if (kind == kFocal)
-    hipLaunchKernelGGL(cls_loss_bwd_kernel<kFocal>, dim3(nb), dim3(kLossThreads), 0, s, a, grad_out, grad_x, gsr, gsc);
-  else if (kind == kSigmoidBce)
-    hipLaunchKernelGGL(cls_loss_bwd_kernel<kSigmoidBce>, dim3(nb), dim3(kLossThreads), 0, s, a, grad_out, grad_x, gsr,
-                       gsc);
-  else
-    hipLaunchKernelGGL(cls_loss_bwd_kernel<kSoftmaxCe>, dim3(nb), dim3(kLossThreads), 0, s, a, grad_out, grad_x, gsr,
-                       gsc);
+  dispatch_kind(kind, [&](auto k) {
+    hipLaunchKernelGGL(cls_loss_bwd_kernel<k()>, dim3(cls_grid(kind, a)), dim3(kLossThreads), 0, as_stream(stream), a,
+                       grad_out, grad_x, gsr, gsc);
+  });
   return check_launch("frh_cls_loss_bwd");
 }
 
 int32_t frh_smooth_l1_fwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const float* y, int64_t ys_i,
                           int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
                           const int32_t* status, float* out, void* workspace, size_t ws_bytes, void* stream) {
-  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
-  int32_t st = check_l1(a);
-  if (st != FRH_OK) return st;
-  FRH_REQUIRE(out, "smooth l1: null output");
-  FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "smooth l1: workspace too small");
-  return launch_l1_fwd(a, SmoothL1Elem{beta}, fan_in(workspace, out, status), stream, "frh_smooth_l1_fwd");
+  return l1_fwd<SmoothL1Elem>(make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta), 0.0f, 0.0f,
+                              status, out, workspace, ws_bytes, stream, "smooth l1", "frh_smooth_l1_fwd");
 }
 
 int32_t frh_balanced_l1_fwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const float* y, int64_t ys_i,
                             int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
                             float alpha, float gamma, const int32_t* status, float* out, void* workspace,
                             size_t ws_bytes, void* stream) {
-  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
-  int32_t st = check_l1(a);
-  if (st != FRH_OK) return st;
-  BalancedL1Elem el;
-  st = make_balanced(beta, alpha, gamma, &el);
-  if (st != FRH_OK) return st;
-  FRH_REQUIRE(out, "balanced l1: null output");
-  FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "balanced l1: workspace too small");
-  return launch_l1_fwd(a, el, fan_in(workspace, out, status), stream, "frh_balanced_l1_fwd");
+  return l1_fwd<BalancedL1Elem>(make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta), alpha, gamma,
+                                status, out, workspace, ws_bytes, stream, "balanced l1", "frh_balanced_l1_fwd");
 }
 
 int32_t frh_det_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int64_t sr, int64_t sc,
@@ -570,22 +503,15 @@ int32_t frh_det_loss_fwd(int32_t kind, const float* x, int64_t n, int64_t c, int
   st = check_l1(r);
   if (st != FRH_OK) return st;
   FRH_REQUIRE(out, "det loss: null output");
-  FRH_REQUIRE(workspace && ws_bytes >= frh_loss_workspace(), "det loss: workspace too small");
-  const int nbc = grid_for(kind == kSoftmaxCe ? n : n * c), nbr = grid_for(rn * rm);
-  char* w = static_cast<char*>(workspace);
-  uint32_t* counter = reinterpret_cast<uint32_t*>(w);
-  float* partial = reinterpret_cast<float*>(w + kCounterBytes);
+  LossWorkspace ws;
+  st = split_workspace(workspace, ws_bytes, "det loss", &ws);
+  if (st != FRH_OK) return st;
+  const int nbc = cls_grid(kind, a), nbr = loss_grid(rn * rm);
   const DetScale o{cls_weight, cls_div, reg_weight, reg_div, out, div_count, status};
-  const dim3 g((unsigned)std::max(nbc, nbr));
-  hipStream_t s = as_stream(stream);
-  if (kind == kFocal)
-    hipLaunchKernelGGL(det_loss_fwd_kernel<kFocal>, g, dim3(kLossThreads), 0, s, a, nbc, r, nbr, counter, partial, o);
-  else if (kind == kSigmoidBce)
-    hipLaunchKernelGGL(det_loss_fwd_kernel<kSigmoidBce>, g, dim3(kLossThreads), 0, s, a, nbc, r, nbr, counter, partial,
-                       o);
-  else
-    hipLaunchKernelGGL(det_loss_fwd_kernel<kSoftmaxCe>, g, dim3(kLossThreads), 0, s, a, nbc, r, nbr, counter, partial,
-                       o);
+  dispatch_kind(kind, [&](auto k) {
+    hipLaunchKernelGGL(det_loss_fwd_kernel<k()>, dim3((unsigned)std::max(nbc, nbr)), dim3(kLossThreads), 0,
+                       as_stream(stream), a, nbc, r, nbr, ws, o);
+  });
   return check_launch("frh_det_loss_fwd");
 }
 
@@ -593,23 +519,16 @@ int32_t frh_smooth_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs
                           int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
                           const float* grad_out, float* grad_x, int64_t gs_i, int64_t gs_j, int64_t gs_l,
                           void* stream) {
-  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
-  int32_t st = check_l1(a);
-  if (st != FRH_OK) return st;
-  return launch_l1_bwd(a, SmoothL1Elem{beta}, grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_smooth_l1_bwd");
+  return l1_bwd<SmoothL1Elem>(make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta), 0.0f, 0.0f,
+                              grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_smooth_l1_bwd");
 }
 
 int32_t frh_balanced_l1_bwd(const float* x, int64_t xs_i, int64_t xs_j, int64_t xs_l, const float* y, int64_t ys_i,
                             int64_t ys_j, const int64_t* label, int64_t n, int64_t m, int64_t n_sel, float beta,
                             float alpha, float gamma, const float* grad_out, float* grad_x, int64_t gs_i,
                             int64_t gs_j, int64_t gs_l, void* stream) {
-  L1Args a = make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta);
-  int32_t st = check_l1(a);
-  if (st != FRH_OK) return st;
-  BalancedL1Elem el;
-  st = make_balanced(beta, alpha, gamma, &el);
-  if (st != FRH_OK) return st;
-  return launch_l1_bwd(a, el, grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_balanced_l1_bwd");
+  return l1_bwd<BalancedL1Elem>(make_l1(x, xs_i, xs_j, xs_l, y, ys_i, ys_j, label, n, m, n_sel, beta), alpha, gamma,
+                                grad_out, grad_x, gs_i, gs_j, gs_l, stream, "frh_balanced_l1_bwd");
 }
 
 }  // extern "C"

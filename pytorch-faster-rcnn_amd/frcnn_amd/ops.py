@@ -2057,29 +2057,40 @@ def _loss_workspace(x):
     return ws
 
 
+def _loss_fwd(entry, x, out_shape, *args):
+    """The tail every fused forward shares: `entry`(*args, status word, out, workspace, its size,
+    stream) on x's device and current stream; returns the f32 output of shape `out_shape`."""
+    out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+    ws = _loss_workspace(x)
+    call(entry, *args, ptr(status_word(x.device)), ptr(out), ptr(ws), ws.numel(), stream_of(x))
+    return out
+
+
+def _cls_call_args(x, target, kind, alpha, gamma):
+    n, c = x.shape
+    return (kind, ptr(x), n, c, x.stride(0), x.stride(1), ptr(target), int(target.dtype == torch.float32),
+            float(alpha), float(gamma))
+
+
+def _cls_bwd(x, target, cfg, g):
+    """frh_cls_loss_bwd: the gradient of the summed loss times the device scalar g."""
+    gx = torch.empty_like(x)
+    g = _f32(g).contiguous()
+    call('frh_cls_loss_bwd', *_cls_call_args(x, target, *cfg), ptr(g), ptr(gx), gx.stride(0), gx.stride(1),
+         stream_of(x))
+    return gx
+
+
 class _ClsLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, kind, alpha, gamma):
-        n, c = x.shape
-        tfloat = int(target.dtype == torch.float32)
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        ws = _loss_workspace(x)
-        call('frh_cls_loss_fwd', kind, ptr(x), n, c, x.stride(0), x.stride(1), ptr(target), tfloat, float(alpha),
-             float(gamma), ptr(status_word(x.device)), ptr(out), ptr(ws), ws.numel(), stream_of(x))
         ctx.save_for_backward(x, target)
-        ctx.cfg = (kind, tfloat, alpha, gamma)
-        return out
+        ctx.cfg = (kind, alpha, gamma)
+        return _loss_fwd('frh_cls_loss_fwd', x, (), *_cls_call_args(x, target, *ctx.cfg))
 
     @staticmethod
     def backward(ctx, g):
-        x, target = ctx.saved_tensors
-        kind, tfloat, alpha, gamma = ctx.cfg
-        n, c = x.shape
-        gx = torch.empty_like(x)
-        g = _f32(g).contiguous()
-        call('frh_cls_loss_bwd', kind, ptr(x), n, c, x.stride(0), x.stride(1), ptr(target), tfloat, float(alpha),
-             float(gamma), ptr(g), ptr(gx), gx.stride(0), gx.stride(1), stream_of(x))
-        return gx, None, None, None, None
+        return _cls_bwd(*ctx.saved_tensors, ctx.cfg, g), None, None, None, None
 
 
 def cls_loss(x, target, kind, alpha=0.25, gamma=2.0):
@@ -2097,28 +2108,37 @@ def cls_loss(x, target, kind, alpha=0.25, gamma=2.0):
     return _ClsLoss.apply(_f32(x), target.contiguous(), int(kind), alpha, gamma)
 
 
-class _SmoothL1(torch.autograd.Function):
+def _l1_call_args(x, y, label, xs, ys, n, m, n_sel, params):
+    """The leading arguments of <stem>_fwd / _bwd; params are the element's floats, beta first."""
+    return (ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
+            *(float(p) for p in params))
+
+
+def _l1_bwd(stem, what, x, y, label, cfg, g):
+    """<stem>_bwd into a zero-filled gradient of x's layout: only the selected, unmasked elements
+    are written."""
+    gx = torch.zeros_like(x)
+    if gx.stride() != x.stride():
+        raise AssertionError('{}: gradient layout differs from the input'.format(what))
+    g = _f32(g).contiguous()
+    xs = cfg[0]
+    call(stem + '_bwd', *_l1_call_args(x, y, label, *cfg), ptr(g), ptr(gx), xs[0], xs[1], xs[2], stream_of(x))
+    return gx
+
+
+class _L1Loss(torch.autograd.Function):
+    """The masked / class-selected regression sum of entry stem `stem` ('frh_smooth_l1' or
+    'frh_balanced_l1') with the element parameters `params` ((beta,) or (beta, alpha, gamma))."""
+
     @staticmethod
-    def forward(ctx, x, y, label, xs, ys, n, m, n_sel, beta):
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        ws = _loss_workspace(x)
-        call('frh_smooth_l1_fwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
-             float(beta), ptr(status_word(x.device)), ptr(out), ptr(ws), ws.numel(), stream_of(x))
+    def forward(ctx, x, y, label, xs, ys, n, m, n_sel, stem, params):
         ctx.save_for_backward(x, y, label)
-        ctx.cfg = (xs, ys, n, m, n_sel, beta)
-        return out
+        ctx.stem, ctx.cfg = stem, (xs, ys, n, m, n_sel, params)
+        return _loss_fwd(stem + '_fwd', x, (), *_l1_call_args(x, y, label, *ctx.cfg))
 
     @staticmethod
     def backward(ctx, g):
-        x, y, label = ctx.saved_tensors
-        xs, ys, n, m, n_sel, beta = ctx.cfg
-        gx = torch.zeros_like(x)
-        if gx.stride() != x.stride():
-            raise AssertionError('smooth_l1: gradient layout differs from the input')
-        g = _f32(g).contiguous()
-        call('frh_smooth_l1_bwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
-             float(beta), ptr(g), ptr(gx), xs[0], xs[1], xs[2], stream_of(x))
-        return gx, None, None, None, None, None, None, None, None
+        return (_l1_bwd(ctx.stem, ctx.stem[len('frh_'):], *ctx.saved_tensors, ctx.cfg, g),) + (None,) * 9
 
 
 def _l1_args(x, y, label, rows_dim):
@@ -2140,7 +2160,7 @@ def _l1_args(x, y, label, rows_dim):
 def smooth_l1_loss(x, y, beta, label=None, rows_dim=0):
     """Summed smooth_l1_loss_v2 of x and y (same shape, 2-D, rows along `rows_dim`),
     counting only rows whose label is > 0 when `label` is given (frh_smooth_l1_fwd/bwd)."""
-    return _SmoothL1.apply(*_l1_args(x, y, label, rows_dim), beta)
+    return _L1Loss.apply(*_l1_args(x, y, label, rows_dim), 'frh_smooth_l1', (beta,))
 
 
 def _l1_class_select_args(reg_out, num_classes, target, label):
@@ -2158,44 +2178,18 @@ def _l1_class_select_args(reg_out, num_classes, target, label):
 def smooth_l1_class_select(reg_out, num_classes, target, label, beta):
     """BBoxHead's regression loss: reg_out [n, 4*C] viewed [n, 4, C], the labelled class's
     deltas of the positive rows against target [n, 4] (any strides), summed."""
-    return _SmoothL1.apply(*_l1_class_select_args(reg_out, num_classes, target, label), beta)
-
-
-class _BalancedL1(torch.autograd.Function):
-    """_SmoothL1 with the balanced-L1 element (frh_balanced_l1_fwd / _bwd)."""
-
-    @staticmethod
-    def forward(ctx, x, y, label, xs, ys, n, m, n_sel, beta, alpha, gamma):
-        out = torch.empty((), dtype=torch.float32, device=x.device)
-        ws = _loss_workspace(x)
-        call('frh_balanced_l1_fwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
-             float(beta), float(alpha), float(gamma), ptr(status_word(x.device)), ptr(out), ptr(ws), ws.numel(),
-             stream_of(x))
-        ctx.save_for_backward(x, y, label)
-        ctx.cfg = (xs, ys, n, m, n_sel, beta, alpha, gamma)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y, label = ctx.saved_tensors
-        xs, ys, n, m, n_sel, beta, alpha, gamma = ctx.cfg
-        gx = torch.zeros_like(x)
-        if gx.stride() != x.stride():
-            raise AssertionError('balanced_l1: gradient layout differs from the input')
-        g = _f32(g).contiguous()
-        call('frh_balanced_l1_bwd', ptr(x), xs[0], xs[1], xs[2], ptr(y), ys[0], ys[1], ptr(label), n, m, n_sel,
-             float(beta), float(alpha), float(gamma), ptr(g), ptr(gx), xs[0], xs[1], xs[2], stream_of(x))
-        return (gx,) + (None,) * 10
+    return _L1Loss.apply(*_l1_class_select_args(reg_out, num_classes, target, label), 'frh_smooth_l1', (beta,))
 
 
 def balanced_l1_loss(x, y, beta, alpha, gamma, label=None, rows_dim=0):
     """Summed balanced_l1_loss (lib/losses.py:158-168) of x and y, as smooth_l1_loss."""
-    return _BalancedL1.apply(*_l1_args(x, y, label, rows_dim), beta, alpha, gamma)
+    return _L1Loss.apply(*_l1_args(x, y, label, rows_dim), 'frh_balanced_l1', (beta, alpha, gamma))
 
 
 def balanced_l1_class_select(reg_out, num_classes, target, label, beta, alpha, gamma):
     """smooth_l1_class_select with the balanced-L1 element."""
-    return _BalancedL1.apply(*_l1_class_select_args(reg_out, num_classes, target, label), beta, alpha, gamma)
+    return _L1Loss.apply(*_l1_class_select_args(reg_out, num_classes, target, label), 'frh_balanced_l1',
+                         (beta, alpha, gamma))
 
 
 class _DetLoss(torch.autograd.Function):
@@ -2204,42 +2198,28 @@ class _DetLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, target, kind, alpha, gamma, wc, rx, ry, rlabel, xs, ys, rn, rm, n_sel, beta, wr, div):
-        n, c = x.shape
-        tfloat = int(target.dtype == torch.float32)
-        out = torch.empty(2, dtype=torch.float32, device=x.device)
-        ws = _loss_workspace(x)
         dcount = div if isinstance(div, torch.Tensor) else None  # device int32 count (sync-free targets)
         hdiv = 1.0 if dcount is not None else float(div)
-        call('frh_det_loss_fwd', kind, ptr(x), n, c, x.stride(0), x.stride(1), ptr(target), tfloat, float(alpha),
-             float(gamma), float(wc), hdiv, ptr(rx), xs[0], xs[1], xs[2], ptr(ry), ys[0], ys[1], ptr(rlabel), rn,
-             rm, n_sel, float(beta), float(wr), hdiv, ptr(dcount), ptr(status_word(x.device)), ptr(out), ptr(ws),
-             ws.numel(), stream_of(x))
+        cls_cfg, l1_cfg = (kind, alpha, gamma), (xs, ys, rn, rm, n_sel, (beta,))
+        out = _loss_fwd('frh_det_loss_fwd', x, 2, *_cls_call_args(x, target, *cls_cfg), float(wc), hdiv,
+                        *_l1_call_args(rx, ry, rlabel, *l1_cfg), float(wr), hdiv, ptr(dcount))
         if dcount is not None:
             # backward divides by the count as f32 (count 0: every row is padding, gradients 0)
             div = dcount.float()
         ctx.save_for_backward(x, target, rx, ry, rlabel)
-        ctx.cfg = (kind, tfloat, alpha, gamma, wc, xs, ys, rn, rm, n_sel, beta, wr, div)
+        ctx.cfg = (cls_cfg, wc, l1_cfg, wr, div)
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, gc, gr):
         x, target, rx, ry, rlabel = ctx.saved_tensors
-        kind, tfloat, alpha, gamma, wc, xs, ys, rn, rm, n_sel, beta, wr, div = ctx.cfg
+        cls_cfg, wc, l1_cfg, wr, div = ctx.cfg
         gx = grx = None
         if gc is not None and ctx.needs_input_grad[0]:
-            g = _f32((gc / div) * wc).contiguous()  # the reference's Div then Mul backward
-            n, c = x.shape
-            gx = torch.empty_like(x)
-            call('frh_cls_loss_bwd', kind, ptr(x), n, c, x.stride(0), x.stride(1), ptr(target), tfloat, float(alpha),
-                 float(gamma), ptr(g), ptr(gx), gx.stride(0), gx.stride(1), stream_of(x))
+            gx = _cls_bwd(x, target, cls_cfg, (gc / div) * wc)  # the reference's Div then Mul backward
         if gr is not None and ctx.needs_input_grad[6]:
-            g = _f32((gr / div) * wr).contiguous()
-            grx = torch.zeros_like(rx)
-            if grx.stride() != rx.stride():
-                raise AssertionError('det loss: gradient layout differs from the input')
-            call('frh_smooth_l1_bwd', ptr(rx), xs[0], xs[1], xs[2], ptr(ry), ys[0], ys[1], ptr(rlabel), rn, rm, n_sel,
-                 float(beta), ptr(g), ptr(grx), xs[0], xs[1], xs[2], stream_of(rx))
-        return gx, None, None, None, None, None, grx, None, None, None, None, None, None, None, None, None, None
+            grx = _l1_bwd('frh_smooth_l1', 'det loss', rx, ry, rlabel, l1_cfg, (gr / div) * wr)
+        return (gx,) + (None,) * 5 + (grx,) + (None,) * 10
 
 
 def det_losses(x, target, kind, alpha, gamma, cls_weight, l1_args, beta, reg_weight, avg_factor):
@@ -2262,30 +2242,30 @@ def det_losses(x, target, kind, alpha, gamma, cls_weight, l1_args, beta, reg_wei
 
 
 # ---------------------------------------------------------------- f1b: GFL head losses, DFL decode
-class _GflLoss(torch.autograd.Function):
-    """QFL / DFL / GIoU losses of the GFL head in one launch (frh_gfl_loss_fwd), one launch
-    backward (frh_gfl_loss_bwd); the positive count and the upstream gradients stay on the device."""
+class _HeadLoss(torch.autograd.Function):
+    """Three losses and the positive count of a one-stage head in one launch (<stem>_fwd), one
+    launch backward (<stem>_bwd); the positive count and the upstream gradients stay on the device.
+    `pack(*ts, cfg)` gives the entries' leading arguments; the first n_out tensors of ts are the
+    head's outputs, which get the gradients."""
 
     @staticmethod
-    def forward(ctx, cls, reg, labels, ltrb, cfg):
-        out = torch.empty(4, dtype=torch.float32, device=cls.device)
-        ws = _loss_workspace(cls)
-        call('frh_gfl_loss_fwd', *_gfl_args(cls, reg, labels, ltrb, cfg), ptr(status_word(cls.device)), ptr(out),
-             ptr(ws), ws.numel(), stream_of(cls))
-        ctx.save_for_backward(cls, reg, labels, ltrb, out)
-        ctx.cfg = cfg
+    def forward(ctx, stem, pack, n_out, cfg, *ts):
+        out = _loss_fwd(stem + '_fwd', ts[0], 4, *pack(*ts, cfg))
+        ctx.save_for_backward(*ts, out)
+        ctx.cfg = (stem, pack, n_out, cfg)
         num_pos = out[3].long()
         ctx.mark_non_differentiable(num_pos)
         return out[0], out[1], out[2], num_pos
 
     @staticmethod
-    def backward(ctx, gc, gd, gb, _):
-        cls, reg, labels, ltrb, out = ctx.saved_tensors
-        g = _f32(torch.stack([gc, gd, gb])).contiguous()
-        gcls, greg = torch.empty_like(cls), torch.empty_like(reg)
-        call('frh_gfl_loss_bwd', *_gfl_args(cls, reg, labels, ltrb, ctx.cfg), ptr(g), ptr(out), ptr(gcls),
-             gcls.stride(0), gcls.stride(1), ptr(greg), greg.stride(0), greg.stride(1), stream_of(cls))
-        return gcls, greg, None, None, None
+    def backward(ctx, g0, g1, g2, _):
+        *ts, out = ctx.saved_tensors
+        stem, pack, n_out, cfg = ctx.cfg
+        g = _f32(torch.stack([g0, g1, g2])).contiguous()
+        grads = [torch.empty_like(t) for t in ts[:n_out]]
+        gargs = [a for t in grads for a in (ptr(t),) + t.stride()]
+        call(stem + '_bwd', *pack(*ts, cfg), ptr(g), ptr(out), *gargs, stream_of(ts[0]))
+        return (None,) * 4 + tuple(grads) + (None,) * (len(ts) - n_out)
 
 
 def _gfl_args(cls, reg, labels, ltrb, cfg):
@@ -2310,38 +2290,11 @@ def gfl_losses(cls_outs, reg_outs, labels, ltrb, bins, stride, reg_mean=0.0, reg
         labels = labels.long()
     cfg = (int(bins), float(stride), float(reg_mean), float(reg_std), int(bool(norm_prob)), float(beta),
            float(cls_weight), float(dfl_weight), float(bbox_weight), float(dfl_avg_factor))
-    return _GflLoss.apply(_f32(cls_outs), _f32(reg_outs), labels.contiguous(), _f32(ltrb).contiguous(), cfg)
+    return _HeadLoss.apply('frh_gfl_loss', _gfl_args, 2, cfg, _f32(cls_outs), _f32(reg_outs), labels.contiguous(),
+                           _f32(ltrb).contiguous())
 
 
 # ---------------------------------------------------------------- f1c: FCOS head losses (no GFL)
-class _FcosLoss(torch.autograd.Function):
-    """Focal / GIoU / centerness losses of the FCOS head in one launch (frh_fcos_loss_fwd), one
-    launch backward (frh_fcos_loss_bwd); the positive count and the upstream gradients stay on the
-    device."""
-
-    @staticmethod
-    def forward(ctx, cls, reg, ctr, labels, ltrb, ctr_t, cfg):
-        out = torch.empty(4, dtype=torch.float32, device=cls.device)
-        ws = _loss_workspace(cls)
-        call('frh_fcos_loss_fwd', *_fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, cfg), ptr(status_word(cls.device)),
-             ptr(out), ptr(ws), ws.numel(), stream_of(cls))
-        ctx.save_for_backward(cls, reg, ctr, labels, ltrb, ctr_t, out)
-        ctx.cfg = cfg
-        num_pos = out[3].long()
-        ctx.mark_non_differentiable(num_pos)
-        return out[0], out[1], out[2], num_pos
-
-    @staticmethod
-    def backward(ctx, gc, gb, gt, _):
-        cls, reg, ctr, labels, ltrb, ctr_t, out = ctx.saved_tensors
-        g = _f32(torch.stack([gc, gb, gt])).contiguous()
-        gcls, greg, gctr = torch.empty_like(cls), torch.empty_like(reg), torch.empty_like(ctr)
-        call('frh_fcos_loss_bwd', *_fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, ctx.cfg), ptr(g), ptr(out),
-             ptr(gcls), gcls.stride(0), gcls.stride(1), ptr(greg), greg.stride(0), greg.stride(1), ptr(gctr),
-             gctr.stride(0), stream_of(cls))
-        return gcls, greg, gctr, None, None, None, None
-
-
 def _fcos_args(cls, reg, ctr, labels, ltrb, ctr_t, cfg):
     reg_mean, reg_std, alpha, gamma, wc, wb, wt = cfg
     return (ptr(cls), cls.shape[0], cls.stride(0), cls.stride(1), ptr(reg), reg.stride(0), reg.stride(1), ptr(ctr),
@@ -2370,8 +2323,8 @@ def fcos_losses(cls_outs, reg_outs, ctr_outs, labels, ltrb, ctr_tars, reg_mean=0
         labels = labels.long()
     cfg = (float(reg_mean), float(reg_std), float(alpha), float(gamma), float(cls_weight), float(bbox_weight),
            float(ctr_weight))
-    return _FcosLoss.apply(_f32(cls_outs), _f32(reg_outs), _f32(ctr_outs), labels.contiguous(),
-                           _f32(ltrb).contiguous(), _f32(ctr_tars).contiguous(), cfg)
+    return _HeadLoss.apply('frh_fcos_loss', _fcos_args, 3, cfg, _f32(cls_outs), _f32(reg_outs), _f32(ctr_outs),
+                           labels.contiguous(), _f32(ltrb).contiguous(), _f32(ctr_tars).contiguous())
 
 
 def dfl_decode(reg, bins, stride, reg_std, reg_mean, cell, img_size):

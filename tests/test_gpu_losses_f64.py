@@ -251,6 +251,7 @@ DET_CASES = {
     'cls_256_reg_1': (('bce', 65537, 1), 1),       # nbc = 256 (capped), nbr = 1
     'cls_1_reg_256': (('bce', 1, 1), 20000),       # nbc = 1, nbr = 256 (capped: 80 000 elements)
     'focal_c4_reg_1': (('focal', 16385, 4), 3),
+    'softmax_256_reg_1': (('softmax', 65537, 3), 1),  # softmax rows at the capped stride nbc = 256
 }
 
 
