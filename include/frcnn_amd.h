@@ -650,6 +650,34 @@ int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, c
                                     const int32_t* level_hw, const int64_t* level_strides, int32_t relu,
                                     void* stream);
 
+/* A VGG16 conv with the max pool behind it (lib/backbones.py:7-31, VGG16: torchvision's
+ * features, Conv2d 3x3 + ReLU, MaxPool2d(2, 2) after layers 2, 4, 7, 10):
+ * y = max_pool2d(act(conv3x3(x, w) + bias), kernel 2, stride 2), no padding, floor mode, in
+ * frh_conv3x3_bias_act's launch pair with the pool in the epilogue: Winograd's 2 x 2 output
+ * tiles start at even coordinates, so a lane holds a whole pool window in registers and stores
+ * its largest value; the full-resolution map is never written.
+ * Arguments and preconditions are frh_conv3x3_bias_act's (cin % 8 == 0, cout % 64 == 0, the
+ * strides, 16-byte alignment, the workspace of frh_conv3x3_workspace; anything else
+ * FRH_EINVAL), except y: contiguous NHWC [n, h / 2, wd / 2, cout] (integer division), which
+ * must not overlap x or the workspace.  An odd last row or column takes part in the
+ * convolution as a neighbour and is dropped by the pool.  h < 2, wd < 2 or n == 0: FRH_OK,
+ * nothing is written.
+ * Contract: for finite inputs the result is bit for bit torch.nn.functional.max_pool2d(., 2) of
+ * frh_conv3x3_bias_act's output for the same arguments (the four values of a window are formed
+ * by the same expressions in the same order; of equal values, -0 and +0 included, the first in
+ * row-major window order is kept, as max_pool2d does).  Fixed summation order, no atomics: the
+ * same bits on every launch.  Capturable: no synchronisation, no allocation, no global state. */
+int32_t frh_conv3x3_bias_act_pool(const float* x, const float* w, const float* bias, float* y, float* workspace,
+                                  int64_t n, int32_t cin, int32_t cout, int32_t h, int32_t wd, int64_t sn,
+                                  int64_t sy, int64_t sx, int32_t relu, void* stream);
+
+/* VGG16's first layer (3 input channels) for the kernel above, whose cin is a multiple of 8:
+ * x contiguous NCHW f32 [n, c, h, w], 1 <= c <= 8, to y contiguous NHWC [n, h, w, 8] with
+ * channels >= c zero (exact zeros in every Winograd sum, so the conv's bits are those of a
+ * c-channel sum).  One thread per pixel, two 16-byte stores.  Any h, w >= 0 (an empty tensor:
+ * FRH_OK, no launch); x and y 16-byte aligned, y not overlapping x (anything else FRH_EINVAL). */
+int32_t frh_nchw_to_nhwc8(const float* x, float* y, int64_t n, int32_t c, int32_t h, int32_t w, void* stream);
+
 /* The prediction convs of a one-stage head (lib/heads/retina_head.py:87, RetinaHead.forward:
  * retina_cls / retina_reg; lib/heads/fcos_head.py:266-281, FCOSHead.forward: fcos_cls / fcos_reg /
  * fcos_center): 3x3, stride 1, padding 1, no groups, no dilation, over every level of the pyramid

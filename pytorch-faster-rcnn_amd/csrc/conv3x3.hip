@@ -1,5 +1,6 @@
-// frh_conv3x3_bias_act, frh_conv3x3_bias_act_levels: the FPN output convs and the RPN head's
-// shared conv (3x3 / stride 1 / padding 1, channels-last f32) as Winograd F(2x2, 3x3) on the
+// frh_conv3x3_bias_act, frh_conv3x3_bias_act_levels, frh_conv3x3_bias_act_pool: the FPN output
+// convs, the RPN head's shared conv and VGG16's convs (3x3 / stride 1 / padding 1, channels-last
+// f32; _pool with the 2x2 max pool that follows in its epilogue) as Winograd F(2x2, 3x3) on the
 // f32 MFMA with the bias (+ ReLU) epilogue on the accumulators (kernels:
 // conv3x3_wino_kernels.h).  The _levels form runs every pyramid level in one launch, with
 // shared (RPN head) or per-level (FPN) weights: the small levels alone have far fewer
@@ -18,6 +19,17 @@ extern "C" int32_t frh_conv3x3_bias_act(const float* x, const float* w, const fl
   const Conv3x3LevelDesc d = {x, w, bias, y, h, wd, sn, sy, sx};
   return conv3x3_launch("frh_conv3x3_bias_act", 1, &d, workspace, (int64_t)16 * cin * cout, n, cin, cout, relu,
                         stream);
+}
+
+// The VGG16 layers ahead of a max pool: the same launch with the pooled epilogue, y
+// [n, h / 2, wd / 2, cout].
+extern "C" int32_t frh_conv3x3_bias_act_pool(const float* x, const float* w, const float* bias, float* y,
+                                             float* workspace, int64_t n, int32_t cin, int32_t cout, int32_t h,
+                                             int32_t wd, int64_t sn, int64_t sy, int64_t sx, int32_t relu,
+                                             void* stream) {
+  const Conv3x3LevelDesc d = {x, w, bias, y, h, wd, sn, sy, sx};
+  return conv3x3_launch<true>("frh_conv3x3_bias_act_pool", 1, &d, workspace, (int64_t)16 * cin * cout, n, cin, cout,
+                              relu, stream);
 }
 
 extern "C" int32_t frh_conv3x3_bias_act_levels(int32_t num_levels, const void* const* xs, const void* const* weights,

@@ -37,6 +37,15 @@
 // cout block slowest inside a level, and dealt to the 8 XCDs in contiguous chunks, so an XCD
 // works through one 1-MB slice of U at a time.  Fixed summation order, no atomics, no split
 // over cin: the same inputs give the same bits on every launch.
+//
+// Pooled form (kPool, frh_conv3x3_bias_act_pool): tiles start at even coordinates, so the four
+// outputs a lane forms per accumulator register are exactly one window of a 2 x 2 / stride-2
+// max pool.  The epilogue forms them as the unpooled one does (same expressions, same order,
+// then bias, then ReLU), keeps the largest and stores it at (oy / 2, ox / 2) of a
+// [n, H / 2, W / 2, cout] output: a quarter of the stores, and no full-resolution map in
+// memory.  An odd last row or column is a neighbour of the convolution and has no window, so
+// the workgroup grid covers 2 (H / 2) x 2 (W / 2) outputs.  The main loop is the same text; the
+// unpooled instantiation has no run-time trace of the pooled one.
 #pragma once
 #include "common.h"
 
@@ -154,6 +163,7 @@ __device__ __forceinline__ uint64_t wg_uniform64(const void* p) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+template <bool kPool>
 static __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kernel(const Conv3x3Args a) {
   // 128 KB, one array: U stages 0, 1 (the LDS-DMA's targets), then V stages 0, 1
   __shared__ __attribute__((aligned(16))) float lds[4 * kWgImage];
@@ -392,7 +402,8 @@ static __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kerne
   // counts as pending again: s_waitcnt vmcnt(0) before all 64 stores, which also retires the
   // store before (stores count in vmcnt), so the stores went out one round trip at a time.
   asm volatile("" : : "v"(bias));
-  float* yb = L.y + (int64_t)img * H * W * a.cout + co;
+  const int PH = H >> 1, PW = W >> 1;  // the pooled extent (kPool)
+  float* yb = kPool ? L.y + (int64_t)img * PH * PW * a.cout + co : L.y + (int64_t)img * H * W * a.cout + co;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int oy = (by * kWgSide + wm * 4 + (r >> 2)) * 2;
@@ -408,15 +419,32 @@ static __global__ void __launch_bounds__(kWgThreads) conv3x3_bias_act_wino_kerne
     o[0][1] = (s0[1] - s0[2]) - s0[3];
     o[1][0] = (s1[0] + s1[1]) + s1[2];
     o[1][1] = (s1[1] - s1[2]) - s1[3];
+    if constexpr (kPool) {
+      // the window in row-major order, a later value replacing the kept one only when it is
+      // larger: max_pool2d's own rule, so a tie of -0 and +0 resolves as it does there
+      float m = 0.0f;
 #pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
+      for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        float v = o[dy][dx];
-        if (has_bias) v = v + bias;
-        if (a.relu) v = fmaxf(v, 0.0f);
-        if (oy + dy < H && ox + dx < W) yb[((int64_t)(oy + dy) * W + (ox + dx)) * a.cout] = v;
-      }
+        for (int dx = 0; dx < 2; ++dx) {
+          float v = o[dy][dx];
+          if (has_bias) v = v + bias;
+          if (a.relu) v = fmaxf(v, 0.0f);
+          m = (dy | dx) == 0 || v > m ? v : m;
+        }
+      const int py = oy >> 1, px = ox >> 1;
+      if (py < PH && px < PW) yb[((int64_t)py * PW + px) * a.cout] = m;
+    } else {
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          float v = o[dy][dx];
+          if (has_bias) v = v + bias;
+          if (a.relu) v = fmaxf(v, 0.0f);
+          if (oy + dy < H && ox + dx < W) yb[((int64_t)(oy + dy) * W + (ox + dx)) * a.cout] = v;
+        }
+    }
   }
 }
 
@@ -434,7 +462,9 @@ struct Conv3x3LevelDesc {
 // distinct weight (consecutive levels with the same w share one) into its slot of ws
 // ([16 * cin * cout] floats each; ws_floats is what the caller provides).  main_launch(grid, a)
 // launches the main kernel: the product's below, a laboratory build of it in the tools library.
-template <class MainLaunch>
+// kPool: the pooled form, y [n, h / 2, w / 2, cout]; a level with no whole window is skipped like
+// an empty one.
+template <bool kPool = false, class MainLaunch>
 inline int32_t conv3x3_launch_with(const char* what, int32_t levels, const Conv3x3LevelDesc* d, float* ws,
                                    int64_t ws_floats, int64_t n, int32_t cin, int32_t cout, int32_t relu,
                                    void* stream, MainLaunch&& main_launch) {
@@ -453,7 +483,10 @@ inline int32_t conv3x3_launch_with(const char* what, int32_t levels, const Conv3
   for (int i = 0; i < levels; ++i) {
     const Conv3x3LevelDesc& s = d[i];
     FRH_REQUIRE(s.h >= 0 && s.w >= 0, "bad sizes");
-    if (n == 0 || s.h == 0 || s.w == 0) continue;
+    // the extent the workgroups cover and y's: the map, or its whole 2 x 2 windows
+    const int32_t eh = kPool ? s.h / 2 * 2 : s.h, ew = kPool ? s.w / 2 * 2 : s.w;
+    const int32_t yh = kPool ? s.h / 2 : s.h, yw = kPool ? s.w / 2 : s.w;
+    if (n == 0 || eh == 0 || ew == 0) continue;
     FRH_REQUIRE(s.x && s.y && s.wt, "null pointer argument");
     FRH_REQUIRE_ALIGNED16(s.x, s.y, s.bias, s.wt);
     if (slots == 0 || tab.w[slots - 1] != s.wt) {
@@ -466,13 +499,13 @@ inline int32_t conv3x3_launch_with(const char* what, int32_t levels, const Conv3
                 "x strides must be multiples of 4 elements and the column stride at least cin");
     const int64_t span = (int64_t)(s.h - 1) * s.sy + (int64_t)(s.w - 1) * s.sx + cin;
     FRH_REQUIRE(span < ((int64_t)1 << 30), "one image of x spans too many elements");
-    const int64_t x_end = (n - 1) * s.sn + span, y_end = n * s.h * s.w * cout;
+    const int64_t x_end = (n - 1) * s.sn + span, y_end = n * yh * yw * cout;
     FRH_REQUIRE(!ranges_overlap(s.y, y_end * 4, s.x, x_end * 4), "y must not alias x");
     FRH_REQUIRE(!ranges_overlap(s.y, y_end * 4, ws, ws_floats * 4), "y must not alias the workspace");
     Conv3x3Level& L = a.lv[a.levels++];
     L.x = s.x, L.u = tab.u[slots - 1], L.bias = s.bias, L.y = s.y;
     L.sn = s.sn, L.sy = (int32_t)s.sy, L.sx = (int32_t)s.sx, L.h = s.h, L.w = s.w;
-    L.by = (s.h + 2 * kWgSide - 1) / (2 * kWgSide), L.bx = (s.w + 2 * kWgSide - 1) / (2 * kWgSide);
+    L.by = (eh + 2 * kWgSide - 1) / (2 * kWgSide), L.bx = (ew + 2 * kWgSide - 1) / (2 * kWgSide);
     L.first = (int32_t)total;
     total += (int64_t)L.by * L.bx * n * (cout / kWgCout);
     FRH_REQUIRE(total < ((int64_t)1 << 30), "too many blocks");
@@ -487,13 +520,14 @@ inline int32_t conv3x3_launch_with(const char* what, int32_t levels, const Conv3
   return check_launch(what);
 }
 
+template <bool kPool = false>
 inline int32_t conv3x3_launch(const char* what, int32_t levels, const Conv3x3LevelDesc* d, float* ws,
                               int64_t ws_floats, int64_t n, int32_t cin, int32_t cout, int32_t relu, void* stream) {
-  return conv3x3_launch_with(what, levels, d, ws, ws_floats, n, cin, cout, relu, stream,
-                             [&](dim3 grid, const Conv3x3Args& a) {
-                               hipLaunchKernelGGL(conv3x3_bias_act_wino_kernel, grid, dim3(kWgThreads), 0,
-                                                  as_stream(stream), a);
-                             });
+  return conv3x3_launch_with<kPool>(what, levels, d, ws, ws_floats, n, cin, cout, relu, stream,
+                                    [&](dim3 grid, const Conv3x3Args& a) {
+                                      hipLaunchKernelGGL(conv3x3_bias_act_wino_kernel<kPool>, grid, dim3(kWgThreads),
+                                                         0, as_stream(stream), a);
+                                    });
 }
 
 }  // namespace frh

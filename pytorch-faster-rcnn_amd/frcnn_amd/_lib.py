@@ -112,6 +112,9 @@ SIGNATURES = {
     'frh_conv3x3_workspace': (c_size, [c_i32, c_i32]),
     'frh_conv3x3_bias_act': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
                                      c_i32, c_vp]),
+    'frh_conv3x3_bias_act_pool': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64,
+                                          c_i64, c_i32, c_vp]),
+    'frh_nchw_to_nhwc8': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'frh_conv3x3_bias_act_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), P(c_vp), P(c_vp), c_vp, c_size, c_i64, c_i32, c_i32,
                                             P(c_i32), P(c_i64), c_i32, c_vp]),
     'frh_conv3x3_out_levels': (c_i32, [c_i32, P(c_vp), P(c_vp), P(c_vp), c_vp, c_vp, c_vp, c_vp, P(c_vp), P(c_vp),

@@ -1,4 +1,7 @@
-"""ResNet backbone (stays on PyTorch-ROCm: MIOpen convs, MFMA f32).
+"""ResNet and VGG16 backbones.
+
+ResNet (PyTorch-ROCm convs, MIOpen, with the fused HIP entries of ops where nothing needs a
+gradient):
 
 Behaviour follows the reference's own ResNet (`lib/backbones.py:133-255`):
 bottleneck blocks with the stride on the 3x3 conv, a 1x1 conv + BN projection
@@ -10,14 +13,21 @@ dicts move between the two frameworks unchanged.
 No pretrained download exists here (no network); `init_weights` uses a
 deterministic Kaiming init when `pretrained` is requested and cannot be
 satisfied, and says so.
+
+VGG16 (reference `lib/backbones.py:7-31`, a wrapper of torchvision's `vgg16.features[:30]`): the
+layer list is restated here under torchvision's parameter names; its thirteen 3x3 convs run as
+the fused Winograd HIP entries, the four max pools in their epilogues (`ops.vgg_conv`,
+`ops.vgg_stem`), where nothing needs a gradient.
 """
 import logging
 
 import torch
 from torch import nn
 
+from . import ops
 from .ops import (bn_act_maxpool, conv1x1_bn_act, conv1x1_pre_fused_ok, conv1x1_s2_bn_act, conv3x3_nchw_bn_act,
                   conv3x3_nchw_fused_ok)
+from .utils import ChannelsLastConvs
 
 # blocks per stage for each depth
 _STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -153,3 +163,59 @@ class ResLayerC5(nn.Module):
 
     def init_weights(self):
         pass
+
+
+# torchvision's vgg16 configuration 'D' up to conv5_3: output channels, 'M' a 2x2 / stride-2 max pool
+_VGG16_LAYERS = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512)
+
+
+class VGG16(ChannelsLastConvs):
+    """The reference's VGG16 (`lib/backbones.py:7-31`): `features` is torchvision's
+    `vgg16.features[:30]` -- thirteen Conv2d 3x3 / padding 1 + ReLU, MaxPool2d(2, 2) at indices
+    4, 9, 16, 23, ending on the ReLU at 29 (stride 16, 512 channels) -- with torchvision's state
+    dict keys (`features.N.weight` / `.bias`), so its pretrained weights load unchanged.
+    `freeze_first_layers` fixes the parameters of `features[:10]`.
+
+    Deviations: forward returns `[x]`, the one-level list every detector
+    consumes (the reference returns the bare tensor, which none of its detectors can take);
+    `classifier_` / `get_classifier` is not mirrored (the fc6 / fc7 pair is
+    `RCNNHead(fc_channels=[4096, 4096])` in the config)."""
+
+    def __init__(self, freeze_first_layers=True, pretrained=True):
+        super().__init__()
+        self.pretrained = pretrained
+        self.freeze_first_layers = freeze_first_layers
+        layers, cin = [], 3
+        for v in _VGG16_LAYERS:
+            if v == 'M':
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+            else:
+                layers += [nn.Conv2d(cin, v, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+                cin = v
+        self.features = nn.Sequential(*layers)
+        if freeze_first_layers:
+            for layer in self.features[:10]:
+                for p in layer.parameters():
+                    p.requires_grad = False
+
+    def forward(self, x):
+        # conv + ReLU (+ the max pool behind it) per step: the fused entries where nothing needs
+        # a gradient (inference; the frozen layers 0-9 in a training step), the modules' ops
+        # otherwise and on the CPU.  No host synchronisation either way.
+        if not x.is_cuda:
+            return [self.features(x)]
+        mods = list(self.features)
+        x = ops.vgg_stem(mods[0], x)
+        for i in range(2, len(mods)):
+            if isinstance(mods[i], nn.Conv2d):
+                pool = i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d)
+                x = ops.vgg_conv(mods[i], x, pool=pool)
+        return [x]
+
+    def init_weights(self):
+        if self.pretrained:
+            logging.warning('VGG16: pretrained weights unavailable offline; using random init')
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+                nn.init.zeros_(m.bias)

@@ -7,7 +7,7 @@ import copy
 
 from torch.optim import SGD
 
-from .backbones import ResNet, ResLayerC5
+from .backbones import ResNet, ResLayerC5, VGG16
 from .necks import FPN, BFP
 from .region import MaxIoUAssigner, RandomSampler, IoUBalancedNegSampler, BasicRoIExtractor
 from .losses import (FocalLoss, SmoothL1Loss, BalancedL1Loss, CrossEntropyLoss, GIoULoss, IoULoss, QualityFocalLoss,
@@ -19,7 +19,7 @@ from .ops import RoIAlign, RoIPool
 _MODULE_LIST = [RetinaNet, CascadeRCNN, FCOS, ResNet, ResLayerC5, FPN, RetinaHead, RPNHead, RCNNHead, FCOSHead,
                 CrossEntropyLoss, SmoothL1Loss, FocalLoss, GIoULoss, IoULoss, QualityFocalLoss, DistributionFocalLoss,
                 BasicRoIExtractor, RoIAlign, RoIPool, SGD, MaxIoUAssigner, RandomSampler, BFP, IoUBalancedNegSampler,
-                BalancedL1Loss, DoubleHead, GARPNHead, BoundedIoULoss]
+                BalancedL1Loss, DoubleHead, GARPNHead, BoundedIoULoss, VGG16]
 
 MODULES = {cls.__name__: cls for cls in _MODULE_LIST}
 

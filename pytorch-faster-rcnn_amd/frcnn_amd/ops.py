@@ -1533,6 +1533,88 @@ def conv3x3_bias_act_levels(convs, xs, relu=False):
     return outs
 
 
+# ---------------------------------------------------------------- VGG16 convolutions
+# Classes (cin, cout, pool) of VGG16's convs, the stem as (3, 64, False), at which
+# tools/bench_vgg.py measured the fused side slower than the modules on the same channels-last
+# input (MIOpen NHWC conv, frh_bias_act_nhwc, max_pool2d; both times in DESIGN section 4): they
+# keep that path.
+_VGG_CONV_EXCLUDED = frozenset()
+
+
+def vgg_conv_fused_ok(conv, x, pool):
+    """Whether vgg_conv takes the fused HIP entry: conv3x3_fused_ok's conditions without the
+    level-size exclusions (measured at 256 channels for the FPN levels), and a class that is
+    dispatched."""
+    return (conv3x3_fused_ok(conv, x, alone=False)
+            and (conv.in_channels, conv.out_channels, bool(pool)) not in _VGG_CONV_EXCLUDED)
+
+
+def _vgg_conv_call(x, weight, bias, cin, cout, pool):
+    """relu(conv3x3(x) + bias), max-pooled 2 x 2 when `pool`, by the fused entries."""
+    n, _, h, w = x.shape
+    sn, _, sy, sx = x.stride()
+    y = _nhwc_empty((n, cout, h // 2, w // 2) if pool else (n, cout, h, w), x.device)
+    call('frh_conv3x3_bias_act_pool' if pool else 'frh_conv3x3_bias_act', ptr(x), ptr(weight), ptr(bias), ptr(y),
+         ptr(_conv3x3_ws(cin, cout, x.device)), n, cin, cout, h, w, sn, sy, sx, 1, stream_of(x))
+    return y
+
+
+def vgg_conv(conv, x, pool=False):
+    """relu(conv(x)), then max_pool2d(., 2) when `pool`, for a 3x3 / stride-1 / padding-1 Conv2d
+    of VGG16: one fused launch pair (frh_conv3x3_bias_act, or frh_conv3x3_bias_act_pool with the
+    pool on the accumulators) where vgg_conv_fused_ok holds; otherwise conv_bias_relu and
+    F.max_pool2d."""
+    if vgg_conv_fused_ok(conv, x, pool):
+        return _vgg_conv_call(x, conv.weight, conv.bias, conv.in_channels, conv.out_channels, pool)
+    y = conv_bias_relu(conv, x)
+    return torch.nn.functional.max_pool2d(y, 2) if pool else y
+
+
+class _PaddedStem(object):
+    """What conv3x3_fused_ok reads of a Conv2d, for the stem conv with its cin padded to 8."""
+
+    def __init__(self, conv, weight):
+        self.weight, self.bias = weight, conv.bias
+        self.in_channels, self.out_channels = 8, conv.out_channels
+        for k in ('kernel_size', 'stride', 'padding', 'dilation', 'groups', 'padding_mode'):
+            setattr(self, k, getattr(conv, k))
+
+
+def _stem_weight8(conv):
+    """The stem's weight [cout, cin, 3, 3] zero-padded to [cout, 8, 3, 3], channels-last; made
+    once per weight version (the memo holds the weight, so its storage is not reused)."""
+    w = conv.weight
+
+    def make():
+        with torch.no_grad():
+            w8 = torch.zeros((w.shape[0], 8, 3, 3), dtype=w.dtype, device=w.device)
+            w8 = w8.contiguous(memory_format=torch.channels_last)
+            w8[:, :w.shape[1]] = w
+            return w8
+    return _memo([w], ('vgg_stem_weight8', w.device, w.data_ptr()), make)
+
+
+def vgg_stem(conv, img):
+    """relu(conv(img)) for VGG16's first conv (3 input channels) on a contiguous NCHW f32 HIP
+    image: frh_nchw_to_nhwc8 pads the channels to 8 in one pass and frh_conv3x3_bias_act runs on
+    it with the zero-padded weight (one cin chunk; the zero channels add exact zeros), under
+    vgg_conv_fused_ok's conditions on the padded tensors.  Otherwise the module and a ReLU."""
+    cin = conv.in_channels
+    ok = (_f32_hip_4d(img) and img.is_contiguous() and 1 <= cin <= 8 and img.shape[1] == cin and img.numel() > 0
+          and conv.weight.dim() == 4 and conv.weight.is_cuda and conv.weight.dtype == torch.float32
+          and (cin, conv.out_channels, False) not in _VGG_CONV_EXCLUDED
+          and _aligned16(img) and not _needs_grad(img, conv.weight, conv.bias))
+    if ok:
+        n, _, h, w = img.shape
+        x8 = torch.empty((n, h, w, 8), dtype=torch.float32, device=img.device).permute(0, 3, 1, 2)
+        stem = _PaddedStem(conv, _stem_weight8(conv))
+        ok = vgg_conv_fused_ok(stem, x8, False)
+    if not ok:
+        return torch.relu(conv(img))
+    call('frh_nchw_to_nhwc8', ptr(img), ptr(x8), n, cin, h, w, stream_of(img))
+    return _vgg_conv_call(x8, stem.weight, stem.bias, 8, conv.out_channels, False)
+
+
 # ---------------------------------------------------------------- one-stage head convolutions
 _CONV3X3_OUT_MAX_COUT = 192
 
