@@ -56,6 +56,22 @@ def _plain(d, x, skip, relu):
     return y
 
 
+def _nan(shape, dev):
+    return torch.full(shape, float('nan'), device=dev)
+
+
+def _pre(d, x, skip, relu, alloc=_nan):
+    """frh_conv1x1_bn_act_pre on the raw input; alloc(shape, device) makes the output (NaN-filled
+    here; tests/test_gpu_guarded_convs.py passes torch.empty under its allocator)."""
+    from frcnn_amd import _lib
+    n, cin, h, w = x.shape
+    cout = d['w'].shape[0]
+    y = alloc((n, cout, h, w), x.device)
+    _lib.call('frh_conv1x1_bn_act_pre', _lib.ptr(x), _lib.ptr(d['w']), _lib.ptr(skip), _lib.ptr(y), *_bn_ptrs(d), EPS,
+              *_bn_ptrs(d, 'p'), EPS, 1, n, cin, cout, h * w, int(relu), _lib.stream_of(x))
+    return y
+
+
 @pytest.mark.parametrize('skip,relu', FLAGS)
 @pytest.mark.parametrize('shape', SHAPES)
 def test_pre_bn_bits_equal_bn_act_then_conv(dev, shape, skip, relu):
@@ -70,18 +86,17 @@ def test_pre_bn_bits_equal_bn_act_then_conv(dev, shape, skip, relu):
     mid = torch.empty_like(x)
     _lib.call('frh_bn_act', p(x), None, p(mid), *_bn_ptrs(d, 'p'), EPS, n, cin, h * w, 1, _lib.stream_of(x))
     ref = _plain(d, mid, sk, relu)
-    y = torch.full((n, cout, h, w), float('nan'), device=dev)
-    _lib.call('frh_conv1x1_bn_act_pre', p(x), p(d['w']), p(sk), p(y), *_bn_ptrs(d), EPS, *_bn_ptrs(d, 'p'), EPS, 1,
-              n, cin, cout, h * w, int(relu), _lib.stream_of(x))
+    y = _pre(d, x, sk, relu)
+    assert y.shape == (n, cout, h, w)
     assert torch.isfinite(y).all()
     assert torch.equal(y, ref)
 
 
-def _s2(d, x, skip, relu):
+def _s2(d, x, skip, relu, alloc=_nan):
     from frcnn_amd import _lib
     n, cin, h, w = x.shape
     cout = d['w'].shape[0]
-    y = torch.full((n, cout, (h + 1) // 2, w // 2), float('nan'), device=x.device)
+    y = alloc((n, cout, (h + 1) // 2, w // 2), x.device)
     _lib.call('frh_conv1x1_s2_bn_act', _lib.ptr(x), _lib.ptr(d['w']), _lib.ptr(skip), _lib.ptr(y), *_bn_ptrs(d), EPS, n,
               cin, cout, h, w, int(relu), _lib.stream_of(x))
     return y

@@ -99,15 +99,21 @@ def _ptrs(ts):
     return (_lib.c_vp * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
-def _entry(xs, ws, bs=(None, None), scales=(None, None), exps=(False, False)):
+def _nan_level(n, c, x):
+    return torch.full((n, c, x.shape[2], x.shape[3]), float('nan'), device=x.device).contiguous(
+        memory_format=torch.channels_last)
+
+
+def _entry(xs, ws, bs=(None, None), scales=(None, None), exps=(False, False), mk=_nan_level):
     """One frh_conv3x3_out_levels launch over the levels xs with the convs ws ([c][3][3][cin]
-    tensors; the second may be empty or None); returns [ys0, ys1] (ys1 empty for one conv)."""
+    tensors; the second may be empty or None); returns [ys0, ys1] (ys1 empty for one conv).
+    mk(n, c, x) makes the channels-last output of c channels for the level x (NaN-filled here;
+    tests/test_gpu_guarded_convs.py passes a torch.empty one under its allocator)."""
     from frcnn_amd import _lib
     n, cin = xs[0].shape[:2]
     two = len(ws) > 1 and ws[1] is not None and ws[1].shape[0] > 0
     c0, c1 = ws[0].shape[0], ws[1].shape[0] if two else 0
-    mk = lambda c, x: torch.full((n, c, x.shape[2], x.shape[3]), float('nan'), device=x.device).contiguous(
-        memory_format=torch.channels_last)
+    mk = functools.partial(mk, n)
     ys0, ys1 = [mk(c0, x) for x in xs], [mk(c1, x) for x in xs] if two else []
     p = _lib.ptr
     _lib.call('frh_conv3x3_out_levels', len(xs), _lib.ptr_array(xs), _lib.ptr_array(ys0),

@@ -72,13 +72,19 @@ def _on_dev(case, kind, dev):
     return d
 
 
-def _entry(xs, wc, bc, wr, br):
-    """One frh_rpn_head1x1_levels launch; returns the outputs interleaved (cls_0, reg_0, cls_1, ...)."""
+def _nan_level(n, c, x):
+    return torch.full((n, c, x.shape[2], x.shape[3]), float('nan'), device=x.device).contiguous(
+        memory_format=torch.channels_last)
+
+
+def _entry(xs, wc, bc, wr, br, mk=_nan_level):
+    """One frh_rpn_head1x1_levels launch; returns the outputs interleaved (cls_0, reg_0, cls_1, ...).
+    mk(n, c, x) makes the channels-last output of c channels for the level x (NaN-filled here;
+    tests/test_gpu_guarded_convs.py passes a torch.empty one under its allocator)."""
     from frcnn_amd import _lib
     n, cin = xs[0].shape[:2]
     cc, cr = wc.shape[0], wr.shape[0]
-    mk = lambda c, x: torch.full((n, c, x.shape[2], x.shape[3]), float('nan'), device=x.device).contiguous(
-        memory_format=torch.channels_last)
+    mk = functools.partial(mk, n)
     cls, reg = [mk(cc, x) for x in xs], [mk(cr, x) for x in xs]
     p = _lib.ptr
     _lib.call('frh_rpn_head1x1_levels', len(xs), _lib.ptr_array(xs), _lib.ptr_array(cls), _lib.ptr_array(reg), p(wc),
